@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- fwd+bwd renders/sec of the rasterizer hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg1] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg1] [--batch B] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one BATCH of `--batch` cameras (default 8; the reference renders a
 camera batch in a Python loop, gs/gaussian_splatting.py:1423-1466): frustum cull + EWA projection + 16x16 tile
@@ -16,8 +17,10 @@ without torchrun, --gpus N > 1 launches its own ranks (torch.distributed.run on 
 on rank 0.
 
 The timed region is exactly K steps between barrier + synchronize pairs; every ctypes table, event and buffer it
-touches is built and used once before it.  The region is repeated (--repeats, default: until 0.5 s have been timed)
-and the median repeat is reported, with the spread next to it.
+touches is built and used once before it.  A plain run times it once and prints the line; --dump-outputs DIR also
+writes what the last timed step computed.  With --full the region is repeated (--repeats, default: until 0.5 s have
+been timed), the median repeat is reported with the spread next to it, and every secondary view, baseline and other
+configuration is measured and added to the line.
 """
 import argparse
 import json
@@ -430,6 +433,26 @@ def model_surfaces(sc, cams, dev, B, K, H, W):
     return res
 
 
+DUMP_BUDGET_FLOATS = 15_000_000  # --dump-outputs: 60 MB of float32 in all
+
+
+def write_outputs(dirname, arrays, budget=DUMP_BUDGET_FLOATS):
+    """--dump-outputs: DIR/<name>.npy per array, float32.  The budget is shared smallest array first; an array beyond its share
+    is written as the same seeded sample of its flattened elements on every run (sorted positions), so that two builds can be
+    compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].size, k))
+    left = budget
+    for i, name in enumerate(names):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float32)
+        take = min(a.size, left // (len(names) - i))
+        if take < a.size:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, take, replace=False))
+            a = a.reshape(-1)[pick]
+        left -= a.size
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 class HostClock:
     """host time spent inside each kind of enqueue call of the timed region"""
 
@@ -451,8 +474,9 @@ def main():
                                   compositing backward, projection backward) on slot j's stream.  run_heads_step: the RGB + heads step.
       * region(first, ...)     -- THE TIMED REGION: barrier + synchronize, exactly K steps, barrier + synchronize, max over ranks; HIP
                                   events on the launch stream bracket every step's compositing launches.  Nothing else is timed.
-      * the block under "timed region" -- W warm-up steps, then region() repeated until 0.5 s are timed; the MEDIAN repeat is `value`.
-    What follows are secondary views, one function each, none of which touches `value`: exact_basis_view (the same region, exact SH
+      * the block under "timed region" -- W warm-up steps, then region() once (with --full: repeated until 0.5 s are timed; the
+                                  MEDIAN repeat is `value`).
+    What follows are secondary views, run with --full only, one function each, none of which touches `value`: exact_basis_view (the same region, exact SH
     basis), the no-gather region (multi-GPU), one_in_flight (one step at a time), heads_report (the RGB + heads step measured like
     `value`), alone_pass (one launch in flight), latency_view (one camera at a time), autograd_surface_view (BatchRenderer + autograd),
     model_surfaces (the model-level call; module level), other_configs (cfg3 / cfg4 / stress lines; module level), trainer_step (the 4 x 512^2 optimisation step, eager and captured; module level), cpu_baseline
@@ -472,7 +496,20 @@ def main():
                     help="backward workgroups per tile (segments of 32 list entries); 1 = one workgroup per tile")
     ap.add_argument("--latency-segments", type=int, default=8,
                     help="the same for the one-render-in-flight pass: uniform work units shorten a lone launch's tail")
-    ap.add_argument("--repeats", type=int, default=0, help="repeats of the timed region (0: until 0.5 s are timed, <= 25)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="repeats of the timed region (0: one, so that exactly --steps steps are timed; with --full until 0.5 s "
+                         "are timed, <= 25, and the median repeat is reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the repeated timed regions, the exact-basis region, the secondary views "
+                         "(RGB + heads path, one step / one launch / one render in flight, autograd and model surfaces), the CPU "
+                         "baseline, the cfg3 / cfg4 / stress lines, the trainer-shaped step and, with several ranks, the region "
+                         "without the gather.  Without it a run sets up, warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rendered images; the "
+                         "gradient of every Gaussian field as one flat vector in field order, grad_fields: mean qvec svec alpha sh, "
+                         "or mean qvec svec color alpha with --path heads) as DIR/<name>.npy, float32, at most 64 MB in all: an "
+                         "array beyond its share "
+                         "is written as a fixed seeded sample of its flattened elements.  The inputs are the same from run to run")
     ap.add_argument("--geo-priority", type=int, default=0,
                     help="1: a slot's geometry stage runs on its own HIGH-priority HIP stream, ahead of the other slot's compositing launch "
                          "instead of in its shadow (measured: 3 333 vs 3 361 renders/s -- the chip is busy either way, "
@@ -488,7 +525,8 @@ def main():
     ap.add_argument("--only-timed", action="store_true",
                     help="profiling runs: nothing but the warm-up and the timed regions launches kernels (no exact-basis region, no "
                          "secondary views, no CPU baseline), so that a rocprofv3 kernel trace of the process averages exactly the "
-                         "launches `value` and `roofline.avg_launch_ms` are made of")
+                         "launches `value` and `roofline.avg_launch_ms` are made of.  Implied without --full; with --full the "
+                         "timed region is still repeated")
     ap.add_argument("--dry-run-lib", default=None, metavar="PATH",
                     help="DRY RUN of the (multi-rank) step loop on the CPU: PATH is a host build of this library's kernels (the "
                          "tests pass one), the process group is gloo, streams and events are stand-ins.  Checks the protocol -- "
@@ -535,6 +573,8 @@ def main():
         cfg4_split = args.config == "cfg4"
         args.only_timed, args.config = True, ("dry4" if cfg4_split else "dry")
         args.batch, args.slots = args.batch or (8 if cfg4_split else 2), args.slots or 2
+    if not args.full:  # a plain run: what the headline needs and nothing else
+        args.only_timed = True
     if args.only_timed:
         args.no_surface = args.no_latency = args.no_cpu_baseline = args.no_heads = args.no_other_configs = True
 
@@ -622,7 +662,10 @@ def main():
     rot_dev = [torch.from_numpy(np.ascontiguousarray(c.c2w[:3, :3]).reshape(-1).copy()).to(dev) for c in cams]
     topleft_dev = [torch.from_numpy(c.topleft).to(dev) for c in cams]
     bg = torch.tensor([0.1, 0.2, 0.3], device=dev)
-    grad_out = torch.randn(H, W, 3, device=dev)
+    # the image gradients are seeded (torch's own generators are not, from process to process): every run of the same arguments
+    # computes the same outputs (--dump-outputs)
+    rng_g = np.random.default_rng(7)
+    grad_out = torch.from_numpy(rng_g.standard_normal((H, W, 3), dtype=np.float32)).to(dev)
     # SH basis: with "auto" (SH degree 3) every step measures the coefficient bound on the device and the launches route on it
     # per view -- nothing about it is decided, or known, on the host while the steps run
     ps_cam = [max(1.0 / ci_.fx, 1.0 / ci_.fy) for ci_ in cis]
@@ -642,7 +685,7 @@ def main():
     want_heads = (args.path == "heads" or not args.no_heads) and "color" in sc and not dry
     if want_heads:
         t["color"] = torch.tensor(sc["color"], device=dev)
-        grad_out6 = torch.randn(H, W, 6, device=dev)
+        grad_out6 = torch.from_numpy(rng_g.standard_normal((H, W, 6), dtype=np.float32)).to(dev)
 
     class Slot:
         def __init__(self, stream):
@@ -922,6 +965,24 @@ def main():
             sl.e_done.record(stream)
             sl.started = True
 
+    def last_step_outputs(j):
+        """what step j handed back, read from its slot once the region has been synchronized: the step's rendered images and the
+        gradient of the loss with respect to every Gaussian field, as ONE flat vector in field order (the per-view gradient blocks
+        in between are the step's own workspace).  One vector, because the compositing backward adds its contributions with
+        float atomics: the gradient is reproducible to rounding at ITS scale, and a field whose gradient is zero in exact
+        arithmetic -- qvec on cfg2's isotropic splats -- holds nothing but rounding residue of the others' size times 1e-17."""
+        sl = slots[j % len(slots)]
+        if args.path == "heads":
+            o = B * 12 * Np
+            images = {"image_rgbd6": sl.out6, "transmittance": sl.T6}
+            grads = (sl.g_mean, sl.g_qvec, sl.g_svec, sl.h_color, sl.hflat[o:o + N])  # mean qvec svec color alpha
+        else:
+            images = {"image_rgb": sl.out}
+            grads = (sl.g_mean, sl.g_qvec, sl.g_svec, sl.g_alpha, sl.g_sh)  # mean qvec svec alpha sh
+        out = {k: v.detach().cpu().numpy() for k, v in images.items()}
+        out["grad_fields"] = torch.cat([g.detach().reshape(-1) for g in grads]).cpu().numpy()
+        return out
+
     state["gather"] = args.gather == "images"
     main_step = run_heads_step if args.path == "heads" else run_step
     if args.path == "heads":
@@ -992,7 +1053,10 @@ def main():
         return {"el": el, "el_local": el_local, "host": host, "fwd_ms": fwd, "bwd_ms": bwd, "host_by_call": dict(clock.acc)}
 
     regions = [region(args.warmup)]
-    n_rep = args.repeats if args.repeats > 0 else int(min(25, max(1, np.ceil(0.5 / regions[0]["el"]))))
+    if args.repeats > 0:
+        n_rep = args.repeats
+    else:
+        n_rep = int(min(25, max(1, np.ceil(0.5 / regions[0]["el"])))) if args.full else 1
     if dist is not None:  # every rank repeats the same number of times
         nr = torch.tensor([n_rep], device=dev)
         dist.broadcast(nr, 0)
@@ -1003,6 +1067,8 @@ def main():
     med = regions[int(order[len(order) // 2])]
     el, fwd_ms, bwd_ms = med["el"], med["fwd_ms"], med["bwd_ms"]
     value = world * B * K / el
+    if args.dump_outputs and rank == 0:  # before any secondary view reuses the slots' buffers
+        write_outputs(args.dump_outputs, last_step_outputs(args.warmup + len(regions) * K - 1))
     # Which kernel rendered which camera is the DEVICE's decision, taken per step from the bound the step measured; it is read
     # back here, after the timed regions, for the report only (gsgen_sh_poly_applies is the same rule on the host).
     S_dev = float(slots[0].bound.item()) if state["bounded"] else 0.0
@@ -1076,7 +1142,7 @@ def main():
 
     # ---- multi-GPU: the same timed region WITHOUT the per-step all_gather (compute scaling and xGMI cost separate) ------------
     no_gather = None
-    if dist is not None and state["gather"]:
+    if dist is not None and state["gather"] and args.full:
         state["gather"] = False
         barrier()
         ng = [region(args.warmup + r * K) for r in range(min(3, n_rep))]

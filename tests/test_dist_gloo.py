@@ -299,6 +299,52 @@ def test_bench_accounting_and_launch_shape():
     assert bench.choose_batch_and_slots(713_016, batch=4, slots=1) == (4, 1)
 
 
+def test_bench_output_dump_fits_its_budget_and_samples_the_same_elements(tmp_path):
+    """--dump-outputs: the budget is shared smallest array first; a larger array is a seeded sample, the same on every call"""
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"small": rng.normal(size=(50, 3)), "mid": rng.normal(size=(400, 4)).astype(np.float32),
+              "big": rng.normal(size=(9, 200, 3)).astype(np.float32)}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, budget=2000)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.size for v in got.values()) <= 2000
+    assert np.array_equal(got["small"], arrays["small"].astype(np.float32))  # within its share: whole, in its shape
+    assert got["mid"].shape == got["big"].shape == ((2000 - 150) // 2,)  # the rest of the budget, halved
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert np.isin(got["big"], arrays["big"]).all()
+
+
+def test_bench_plain_dry_run_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run (no --full) times ONE region of exactly --steps steps and adds nothing else to the line; --dump-outputs writes
+    the last timed step's images and its gradient of every Gaussian field (one flat vector), the same on every run of the same
+    arguments (the host build of the kernels sums in a fixed order: bit for bit here)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    subprocess.check_call(["make", "-C", os.path.join(root, "oracle"), "-s", "emu"])
+    emu = os.path.join(root, "oracle", "_build", "libgsgen_emu.so")
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run-lib", emu, "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / d)], cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        res = json.loads(lines[0])
+        assert res["steps"] == 3 and res["timing"]["repeats"] == 1 and res["ms_per_step"] > 0
+        assert abs(res["timing"]["timed_region_s"] / 3 * 1e3 - res["ms_per_step"]) < 1e-9
+        assert not {"exact_basis", "heads_path", "one_step_in_flight", "cpu_baseline", "other_configs"} & set(res)
+        assert sorted(os.listdir(tmp_path / d)) == ["grad_fields.npy", "image_rgb.npy"]
+        dumps.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("image_rgb", "grad_fields")})
+    B, H, W = res["config"]["cameras_per_step"], *res["config"]["image"]
+    assert dumps[0]["image_rgb"].shape == (B, H, W, 3) and dumps[0]["grad_fields"].shape == (60 * (3 + 4 + 3 + 1 + 48),)
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, n
+        assert np.array_equal(a, dumps[1][n]), n
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_step_loop_dry_run_with_several_ranks(world):
     """nobody has run bench.py with more than one rank before the driver's 8-GPU run.  `--dry-run-lib` runs
@@ -339,7 +385,7 @@ def test_bench_step_loop_dry_run_eight_ranks_on_the_cfg4_camera_split():
     subprocess.check_call(["make", "-C", os.path.join(root, "oracle"), "-s", "emu"])
     emu = os.path.join(root, "oracle", "_build", "libgsgen_emu.so")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--config", "cfg4", "--dry-run-lib", emu,
-                        "--steps", "2", "--warmup", "1"], cwd=root, capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full"], cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

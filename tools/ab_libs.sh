@@ -7,7 +7,7 @@ for r in $(seq 1 $rounds); do
   for v in "$@"; do
     lib=${v%%@*}; extra=""; [ "$lib" != "$v" ] && extra=$(echo "${v#*@}" | tr '+' ' ')
     if [ "$lib" = "-" ]; then envs=""; else envs="GSGEN_HIP_LIB=$lib"; fi
-    env $envs timeout 240 python bench.py --steps 40 --warmup 10 --no-surface --no-cpu-baseline $extra 2>/dev/null | python -c "
+    env $envs timeout 240 python bench.py --full --steps 40 --warmup 10 --no-surface --no-cpu-baseline $extra 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ tag=$1; cfg=$2; mode=${3:-full}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
 extra=""; [ "$mode" = quick ] && extra="--no-cpu-baseline"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --config $cfg $extra > $O/${tag}_bench_${cfg}.json 2> $O/${tag}_bench_${cfg}.err; echo "bench $cfg rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --config $cfg $extra > $O/${tag}_bench_${cfg}.json 2> $O/${tag}_bench_${cfg}.err; echo "bench $cfg rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/${tag}_bench_${cfg}.json")); h=r.get("heads_path") or {}

@@ -5,8 +5,8 @@ timeout 1500 python -m pytest tests -m gpu -q --maxfail=12 -p no:cacheprovider >
 bash tools/gpu_final.sh r06 2>&1 | tail -70
 cd $R
 for r in 1 2; do
-  GSGEN_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_bench_cfg2_force_dist_$r.json 2>/dev/null
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_bench_cfg2_plain_same_box_$r.json 2>/dev/null
+  GSGEN_BENCH_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_bench_cfg2_force_dist_$r.json 2>/dev/null
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_bench_cfg2_plain_same_box_$r.json 2>/dev/null
 done
 python - <<'PY' | tee $O/r06_force_dist_agreement.txt
 import json

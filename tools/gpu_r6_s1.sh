@@ -4,7 +4,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/r06_s1
 : > $O/r06_s1_ab_heads_moments.txt
 for r in 1 2; do
   for form in plain moments; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --heads-grad-form $form 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --heads-grad-form $form 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/r06_s11_gpu_tests.log 2>&1; echo "pytest rc=$?"; tail -3 $O/r06_s11_gpu_tests.log
 timeout 300 python tools/prof_model_step.py 30 2> $O/r06_s11_model_step.txt; cat $O/r06_s11_model_step.txt
 timeout 300 python tools/bench_step.py 2>/dev/null | cut -c1-260; timeout 300 python tools/bench_step.py --graph 2>/dev/null | cut -c1-260
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-latency --no-other-configs 2>/dev/null > $O/r06_s11_bench_cfg2_quick.json
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-latency --no-other-configs 2>/dev/null > $O/r06_s11_bench_cfg2_quick.json
 python - <<PY
 import json
 r=json.load(open("$O/r06_s11_bench_cfg2_quick.json")); h=r.get("heads_path") or {}

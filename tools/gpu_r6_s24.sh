@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 out=$O/r06_s24_ab_bwd_priority.txt; : > $out
 for r in 1 2; do for v in "" "--bwd-priority 1"; do
-  timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-other-configs $v 2>/dev/null | python -c "
+  timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-other-configs $v 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 out=$O/r06_s29_ab_slots.txt; : > $out
 for r in 1 2; do for v in "--slots 2" "--slots 3" "--slots 4" "--slots 5"; do
-  timeout 400 python bench.py --steps 24 --warmup 6 --no-cpu-baseline --no-surface --no-latency --no-other-configs $v 2>/dev/null | python -c "
+  timeout 400 python bench.py --full --steps 24 --warmup 6 --no-cpu-baseline --no-surface --no-latency --no-other-configs $v 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ export AB_ARGS=""
 : > $O/r06_s3_ab_sh_moments.txt
 for r in 1 2; do
   for form in plain moments; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --sh-grad-form $form 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --sh-grad-form $form 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -3,7 +3,7 @@
 # one Python cannot drive both libraries) against this tree, alternating
 R=$GRAFT_REPO_ROOT; cd $R; O=$R/gpurun_out; out=$O/r06_s34_ab_sh_pixel_size_dev.txt; : > $out
 for r in 1 2; do for t in . _prev_tree . _prev_tree; do
-  ( cd $R/$t; timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-other-configs 2>/dev/null ) | python -c "
+  ( cd $R/$t; timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-other-configs 2>/dev/null ) | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

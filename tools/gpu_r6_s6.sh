@@ -4,7 +4,7 @@ timeout 1500 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/r06_s6
 : > $O/r06_s6_ab_heads_chol.txt
 for r in 1 2; do
   for v in "--no-heads-chol" ""; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency $v 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency $v 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 # round 6, session 8: the driver's command as the driver runs it (wall clock), heads variants again after the background fix
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 t0=$(date +%s.%N)
-timeout 900 python bench.py > $O/r06_s8_bench_cfg2.json 2> $O/r06_s8_bench_cfg2.err; echo "bench rc=$? wall $(python -c "import time;print(round(time.time()-$t0,1))") s"
+timeout 900 python bench.py --full > $O/r06_s8_bench_cfg2.json 2> $O/r06_s8_bench_cfg2.err; echo "bench rc=$? wall $(python -c "import time;print(round(time.time()-$t0,1))") s"
 python - <<PY
 import json
 r=json.load(open("$O/r06_s8_bench_cfg2.json")); h=r.get("heads_path") or {}

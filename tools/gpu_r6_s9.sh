@@ -6,7 +6,7 @@ for r in 1 2; do
  for stress in "" "--outlier-fraction 0.01" "--outlier-fraction 0.05" "--focal-scale 0.7"; do
   [ $r = 2 ] && [ -n "$stress" ] && continue
   for v in "--always-fallback" ""; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-heads --no-other-configs $stress $v 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-surface --no-latency --no-heads --no-other-configs $stress $v 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,7 +8,7 @@ if [ "$tests" = tests ]; then
   timeout 1500 python -m pytest tests -m gpu -q --maxfail=12 -p no:cacheprovider > $O/${tag}_gpu_tests.log 2>&1; echo "pytest rc=$?" >> $O/${tag}_gpu_tests.log
   tail -6 $O/${tag}_gpu_tests.log
 fi
-timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench_cfg2.json 2> $O/${tag}_bench_cfg2.err; echo "bench rc=$?"
+timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench_cfg2.json 2> $O/${tag}_bench_cfg2.err; echo "bench rc=$?"
 python - <<PY
 import json
 r=json.load(open("$O/${tag}_bench_cfg2.json"))
