@@ -565,6 +565,9 @@ def test_batched_fused_heads_match_oracle(detach, pipeline):
         want["alpha"][m] += ga; want["color"][m] += r[2]
     for k in keys:
         assert rel_err(P_[k].grad.cpu().numpy(), want[k]) < 2e-3, k
+        # per Gaussian as well: a row whose gradient is 1 % of the tensor's largest is held to its own magnitude
+        assert scenes.per_gaussian_grad_error(P_[k].grad.cpu().numpy(), want[k])[0] <= 1.0, (k, scenes.per_gaussian_grad_error(
+            P_[k].grad.cpu().numpy(), want[k]))
 
 
 def test_full_size_cfg2():
