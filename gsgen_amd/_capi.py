@@ -147,7 +147,15 @@ SIZE_FUNCS = {
     "gsgen_frame_batch_workspace_bytes": [u32],
     "gsgen_legacy_sort_workspace_bytes": [u32, u32],
 }
-EXPORTS = sorted(list(SIGNATURES) + list(SIZE_FUNCS) + list(PTR_FUNCS)
+# entry points bound only where the library has them: the CPU emulator build (oracle/Makefile `emu`) compiles a fixed source list
+# without knn.hip, and its tests load it through this class; the in-tree library exports them (EXPORTS, tests/test_cpu_host.py)
+OPTIONAL_SIGNATURES = {
+    "gsgen_knn": [vp, u32, u32, vp, vp, vp, sz, vp],
+}
+OPTIONAL_SIZE_FUNCS = {
+    "gsgen_knn_workspace_bytes": [u32, u32],
+}
+EXPORTS = sorted(list(SIGNATURES) + list(SIZE_FUNCS) + list(PTR_FUNCS) + list(OPTIONAL_SIGNATURES) + list(OPTIONAL_SIZE_FUNCS)
                  + ["gsgen_version", "gsgen_error_string", "gsgen_kernel_variant", "gsgen_sh_poly_applies"])
 
 
@@ -195,6 +203,14 @@ class Lib:
             fn.argtypes = argt
             fn.restype = sz
             setattr(self, name[len("gsgen_"):], fn)
+        for table, restype in ((OPTIONAL_SIGNATURES, i32), (OPTIONAL_SIZE_FUNCS, sz)):
+            for name, argt in table.items():
+                fn = getattr(self.cdll, name, None)
+                if fn is None:
+                    continue  # (a library built without this source: the attribute stays absent)
+                fn.argtypes = argt
+                fn.restype = restype
+                setattr(self, name[len("gsgen_"):], self._checked(name, fn) if restype is i32 else fn)
 
     def _checked(self, name, fn):
         err = self.cdll.gsgen_error_string

@@ -25,6 +25,7 @@ SOURCES = {
     "geometry.hip": ["-ffp-contract=off"],
     "binning.hip": [],
     "legacy.hip": ["-ffp-contract=off"],
+    "knn.hip": ["-ffp-contract=off"],  # dist2 bit-identical to an fp32 brute force (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three
 # cross-file helpers used to be exported beside them)

@@ -244,3 +244,59 @@ class AdaptiveControl:
             new_stats.max_radii2d.copy_(maxr)
         self.last_info = info
         return new_opt, new_stats, True
+
+
+# ---- compatness densification (gs/gaussian_splatting.py:634-743) and its penalty (:1051-1094) --------------------------------
+# Pure torch on a given neighbour index (any device): the neighbours come from gsgen_amd.knn on the GPU, or from a test's record.
+# The arithmetic is the reference's, operation for operation (the golden tests compare bits); the helpers are this project's.
+
+def distance_to_gaussian_surface(mean, svec, rotmat, query):
+    """Radius of each Gaussian (centre `mean`, scales `svec`, rotation `rotmat`) along the unit direction towards `query`, in the
+    reference's model of the surface (utils/ops.py:137-157).  With u the direction in the Gaussian's frame and rho = |u_xy|:
+        planar = s_x^2 (u_x / rho)^2 + s_y^2 (u_y / rho)^2,   radius = sqrt(s_z^2 u_z^2 + planar^2 rho^2 + 1e-10)
+    (planar enters squared, as in the reference; rho carries a 1e-10 guard under its root)."""
+    local = torch.einsum("bij,bj->bi", rotmat.transpose(-1, -2), query - mean)
+    u = torch.nn.functional.normalize(local, dim=-1)
+    ux, uy, uz = u[..., 0], u[..., 1], u[..., 2]
+    rho = torch.sqrt(ux**2 + uy**2 + 1e-10)
+    planar = svec[..., 0] ** 2 * (ux / rho) ** 2 + svec[..., 1] ** 2 * (uy / rho) ** 2
+    return torch.sqrt(svec[..., 2] ** 2 * uz**2 + planar**2 * rho**2 + 1e-10)
+
+
+def compat_gaps(mean, svec, rotmat, idx):
+    """Each Gaussian i against its neighbour j = idx[i] -> (|m_j - m_i|, radius of i towards j, radius of j towards i, m_j).
+    Differentiable through the gathered neighbour values (the penalty's gradient reaches the neighbours that way)."""
+    m_nb = mean[idx]
+    r_nb = distance_to_gaussian_surface(m_nb, svec[idx], rotmat[idx], mean)
+    r_self = distance_to_gaussian_surface(mean, svec, rotmat, m_nb)
+    return torch.norm(m_nb - mean, dim=-1), r_self, r_nb, m_nb
+
+
+def compatness_new_rows(raw, svec, svec_inv_act, idx):
+    """One neighbour column (:634-680): wherever the surfaces of Gaussian i and its neighbour idx[i] leave a gap
+    (r_i + r_j < |m_j - m_i|), a new Gaussian in that gap -> raw fields of the new rows (the keys of `raw`).
+      mean  m_i + (m_j - m_i) / |m_j - m_i| * (|m_j - m_i| + r_i - r_j) / 2
+      svec  svec_inv_act(gap / 6) on all three axes, gap = |m_j - m_i| - r_i - r_j
+      other fields copied from Gaussian i.
+    raw: the raw (pre-activation) fields; svec: the activated scales."""
+    mean = raw["mean"]
+    dist, r_self, r_nb, m_nb = compat_gaps(mean, svec, rotmat_of_qvec(raw["qvec"]), idx)
+    gap_open = (r_self + r_nb) < dist
+    unit = (m_nb - mean) / dist[..., None]
+    rows = {}
+    for k, v in raw.items():
+        if k == "mean":
+            rows[k] = (mean + unit * (dist + r_self - r_nb)[..., None] / 2.0)[gap_open]
+        elif k == "svec":
+            gap = (dist - r_self - r_nb)[gap_open]
+            rows[k] = svec_inv_act(gap[..., None].expand(-1, svec.shape[-1]) / 6.0)
+        else:
+            rows[k] = v[gap_open]
+    return rows
+
+
+def compatness_rows(raw, svec, svec_inv_act, idx):
+    """All neighbour columns of idx [N, K] (column 0 = the nearest OTHER Gaussian, :682-696): the new rows of each column, the
+    columns one after the other"""
+    cols = [compatness_new_rows(raw, svec, svec_inv_act, idx[:, c]) for c in range(idx.shape[1])]
+    return {k: torch.cat([col[k] for col in cols], dim=0) for k in cols[0]}

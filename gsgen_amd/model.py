@@ -21,7 +21,8 @@ drop-in (gsgen_amd.install_as_gs) stays available for code that calls the 23 nam
 (bench.py reports both: `dropin_gs_surface` against `model_surface`).
 
 What is NOT carried over (raises NotImplementedError when configured or called): normal_as_rgb, pbr / specular shading, MLPBackground
-(tinycudann), overrides, the penalty losses behind auxiliary_loss, densify_by_compatness, the gradient-mask windows of update().
+(tinycudann), overrides, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of update().  Penalty losses and
+compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
 The densify / prune policies themselves live in gsgen_amd.densify (this class delegates; AdaptiveControl is the multi-rank form on a
 FusedAdam), the flat-buffer optimiser in gsgen_amd.optim.
 """
@@ -90,6 +91,35 @@ def _lr_schedule(spec):
         w = min(max((step - s0) / (s1 - s0), 0.0), 1.0)
         return v1 - (v1 - v0) * float(np.sqrt(w)) if root else v0 + (v1 - v0) * w
     return f
+
+
+def schedule_value(spec, step, max_steps=None):
+    """A scalar that may follow the training step -- how the reference's configs write penalty weights (utils/misc.py:218-260):
+        number                                  constant
+        [v0, v1, s1]                            the same as [0, v0, v1, s1]
+        [s0, v0, v1, s1]                        linear from (s0, v0) to (s1, v1), constant outside
+        [s0, v0, v1, s1, "linear" | "sqrt"]     that ramp, or v1 - (v1 - v0) * sqrt(t) with t the ramp's position in [0, 1]
+    A float s1 is a fraction of max_steps; the reference then evaluates the ramp at step s1 * max_steps, and so does this."""
+    if isinstance(spec, (int, float)):
+        return spec
+    spec = _to_plain(spec)
+    if not isinstance(spec, list) or len(spec) not in (3, 4, 5):
+        raise ValueError(f"gsgen_amd.model: a scheduled scalar is a number or a list of 3, 4 or 5 entries, not {spec!r}")
+    if len(spec) == 3:
+        spec = [0, *spec]
+    s0, v0, v1, s1 = spec[:4]
+    kind = spec[4] if len(spec) == 5 else "linear"
+    if kind not in ("linear", "sqrt"):
+        raise NotImplementedError(f"gsgen_amd.model: scheduled scalar of kind {kind!r} (linear and sqrt are supported)")
+    at = step
+    if kind == "linear" and isinstance(s1, float):
+        if max_steps is None:
+            raise ValueError(f"gsgen_amd.model: {spec!r} ends at a fraction of the run, which needs max_steps")
+        at = s1 * max_steps
+    t = max(min(1.0, (at - s0) / (s1 - s0)), 0.0)
+    if kind == "sqrt":
+        return v1 - (v1 - v0) * float(np.sqrt(t))
+    return v0 + (v1 - v0) * t
 
 
 class _Background(nn.Module):
@@ -417,18 +447,31 @@ class GaussianSplattingRenderer(nn.Module):
         if not (self.densify_enabled and _get(c, "warm_up", 0) <= step <= _get(c, "end", 0)
                 and D.step_check(step, int(_get(c, "period", 1000)), True)):
             return 0
-        dc = D.DensifyConfig(enabled=True, type="legacy" if _get(c, "use_legacy", True) else "official",
+        kind = str(_get(c, "type", "official"))
+        use_legacy = bool(_get(c, "use_legacy", True))
+        dc = D.DensifyConfig(enabled=True, type="legacy" if use_legacy else "official",
                              warm_up=int(_get(c, "warm_up", 0)), end=int(_get(c, "end", 0)), period=int(_get(c, "period", 1000)),
                              mean2d_thresh=float(_get(c, "mean2d_thresh", 0.02)), split_thresh=float(_get(c, "split_thresh", 0.02)),
                              n_splits=int(_get(c, "n_splits", 2)), split_shrink=float(_get(c, "split_shrink", 0.8)))
         raw, n0 = self._raw(), self.N
-        if dc.type == "legacy":
-            raw, info = D.densify_legacy(raw, self.svec.data, self.svec_inv_act, self.mean_2d_grad_accum, self.cnt, dc)
-            moments = None
-        else:
-            raw, moments, info = D.densify_official(raw, self._moments(), {"svec": self.svec_act, "svec_inv": self.svec_inv_act},
-                                                    self.mean_2d_grad_accum, self.cnt, dc)
-        self._adopt(raw, moments, step)
+        # :756-816: `use_legacy` runs the legacy split / clone and then the compatness step its type names; otherwise the type picks
+        # one method ("scale" and "all" still take the official one here)
+        compat = ("shrink_then_compatness" if "shrink_then_compatness" in kind else "compatness" if "compatness" in kind else None)
+        if not use_legacy and kind not in ("compatness", "shrink_then_compatness"):
+            compat = None
+        info = {}
+        if use_legacy or compat is None:
+            if dc.type == "legacy":
+                raw, info = D.densify_legacy(raw, self.svec.data, self.svec_inv_act, self.mean_2d_grad_accum, self.cnt, dc)
+                moments = None
+            else:
+                raw, moments, info = D.densify_official(raw, self._moments(), {"svec": self.svec_act, "svec_inv": self.svec_inv_act},
+                                                        self.mean_2d_grad_accum, self.cnt, dc)
+            self._adopt(raw, moments, step)
+        if compat == "shrink_then_compatness":
+            info["num_compat"] = self.densify_by_shrink_then_compatness(float(_get(c, "surface_shrink", 1.5)), K=int(_get(c, "K", 3)))
+        elif compat == "compatness":
+            info["num_compat"] = self.densify_by_compatness(K=int(_get(c, "K", 3)))
         self.reset_densify_info()
         if verbose:
             print(f"[gsgen_amd] densify at step {step}: {n0} -> {self.N} Gaussians {info}")
@@ -460,17 +503,137 @@ class GaussianSplattingRenderer(nn.Module):
             print(f"[gsgen_amd] prune at step {step}: {n0} -> {self.N} Gaussians {counts}")
         return n0 - self.N
 
+    # ---- compatness densification (gs/gaussian_splatting.py:481-522, :634-743) -------------------------------------------------
+    _raw_attr = {"mean": "mean", "qvec": "qvec", "svec": "svec_before_activation", "color": "color_before_activation",
+                 "alpha": "alpha_before_activation"}
+
+    @torch.no_grad()
+    def densify_with_new_params(self, new_params):
+        """:517-522 -> densify_on_optimizer :481-515: append the rows of new_params (raw fields) to every parameter; every non-`bg`
+        optimiser group gets its parameter replaced and its Adam tensors extended with zeros (`step` is kept), the `bg` group is
+        left alone.  The densify statistics are NOT reset here (densify() does that afterwards, :817)."""
+        opt = getattr(self, "optimizer", None)
+        groups = {g["name"]: g for g in opt.param_groups} if opt is not None else {}
+        for name, attr in self._raw_attr.items():
+            old = getattr(self, attr)
+            ext = new_params[name].to(old.dtype)
+            param = nn.Parameter(torch.cat((old.data, ext), dim=0).requires_grad_(True))
+            g = groups.get(name)
+            if g is not None:
+                st = opt.state.pop(g["params"][0], None)
+                if st is not None:
+                    for k in list(st.keys()):
+                        if torch.is_tensor(st[k]) and st[k].ndim != 0:
+                            st[k] = torch.cat((st[k], torch.zeros_like(ext)), dim=0)
+                    opt.state[param] = st
+                g["params"][0] = param
+            setattr(self, attr, param)
+        self.N = self.mean.data.shape[0]
+
+    @torch.no_grad()
     def densify_by_compatness(self, K=1):
-        raise NotImplementedError("gsgen_amd.model: densify_by_compatness (gs/gaussian_splatting.py:682-739, the upsample-tune stage of "
-                                  "trainer.py:796-801) is outside the rasterizer path this library replaces (SURVEY.md section 2)")
+        """:682-696: for each Gaussian and each of its K nearest other Gaussians (gsgen_amd.knn, a K + 1 search), a new Gaussian
+        in the gap where the two surfaces do not touch; -> the number of new Gaussians"""
+        from . import densify as D
+        from .knn import K_nearest_neighbors
+        _, idx = K_nearest_neighbors(self.mean.data, K=int(K) + 1)
+        new = D.compatness_rows(self._raw(), self.svec.data, self.svec_inv_act, idx)
+        self.densify_with_new_params(new)
+        return new["mean"].shape[0]
+
+    @torch.no_grad()
+    def densify_by_shrink_then_compatness(self, shrink_factor, K=3):
+        """:741-743: every scale divided by shrink_factor, then densify_by_compatness(K)"""
+        self.svec = self.svec / shrink_factor
+        return self.densify_by_compatness(K=K)
+
+    # ---- penalty losses (gs/gaussian_splatting.py:950-1122) ------------------------------------------------------------------
+    # Each _penalty_<key> returns the unweighted term (and extra scalars to log); auxiliary_loss weighs, logs and sums them.
+    _PENALTY_KINDS = {"alpha": ("uniform_l1", "uniform_l2", "center_weighted"),
+                      "mean": ("uniform_l1", "uniform_l2", "weighted_l1", "weighted_l2"), "compat": ("l1", "l2")}
+    _PENALTY_UNSUPPORTED = {"move": "needs the previous step's means, which the reference never records",
+                            "specular": "belongs to pbr shading, which this class does not implement",
+                            "normal": "belongs to pbr shading, which this class does not implement"}
+
+    def _penalty_node(self, key):
+        return _get(_get(self.cfg, "penalty"), key)
+
+    def _penalty_kind(self, key):
+        kind = _get(self._penalty_node(key), "type")
+        if kind not in self._PENALTY_KINDS[key]:
+            raise ValueError(f"gsgen_amd.model: penalty.{key}.type is {kind!r}; expected one of {', '.join(self._PENALTY_KINDS[key])}")
+        return kind
+
+    def _penalty_alpha(self):
+        """opacity: its mean, its mean square, or its mean weighted by the (constant) distance of each centre from the origin"""
+        kind = self._penalty_kind("alpha")
+        if kind == "center_weighted":
+            return torch.mean(self.mean.detach().norm(dim=-1) * self.alpha), {}
+        return torch.mean(self.alpha if kind == "uniform_l1" else self.alpha**2), {}
+
+    def _penalty_mean(self):
+        """distance of the centres from the origin: l1 / l2, optionally weighted by its own (constant) value"""
+        kind = self._penalty_kind("mean")
+        r = self.mean.norm(dim=-1)
+        if kind == "uniform_l1":
+            return torch.mean(r), {}
+        if kind == "uniform_l2":
+            return torch.mean(r**2), {}
+        if kind == "weighted_l1":
+            return torch.mean(r.detach() * self.mean.norm(dim=-1)), {}
+        return torch.mean(r.detach() ** 2 * self.mean.norm(dim=-1) ** 2), {}
+
+    def _penalty_scale(self):
+        """summed volume (product of the three scales)"""
+        return self.svec.prod(dim=-1).sum(), {}
+
+    def _penalty_NN(self):
+        """mean distance from each centre to its nearest other centre (the neighbour's position is a constant)"""
+        from .knn import nearest_neighbor
+        nn_pos, _ = nearest_neighbor(self.mean)
+        return torch.mean((self.mean - nn_pos).norm(dim=-1)), {}
+
+    def _penalty_compat(self):
+        """mean over the Gaussians of the gap between their surface and their nearest neighbour's (zero where they touch), l1 or
+        l2; the gradient flows through the gathered neighbour values"""
+        from . import densify as D
+        from .knn import nearest_neighbor
+        kind = self._penalty_kind("compat")
+        _, nb = nearest_neighbor(self.mean)
+        dist, r_self, r_nb, _ = D.compat_gaps(self.mean, self.svec, D.rotmat_of_qvec(self.qvec), nb)
+        gap_open = (r_self + r_nb) < dist
+        gap = dist - r_self - r_nb
+        term = torch.mean((gap if kind == "l1" else gap**2) * gap_open)
+        return term, {"effective_rate": lambda: torch.sum(gap_open).item() / self.N}
 
     def auxiliary_loss(self, step, writer=None):
-        """trainer.py:469: the sum of the configured penalty losses (gs/gaussian_splatting.py:950-1122).  They are plain torch on the
-        parameters, outside the rasterizer path: an empty `penalty` config gives the zero the trainer adds; a configured one raises."""
-        keys = list(_get(self.cfg, "penalty", None) or [])
-        if keys:
-            raise NotImplementedError(f"gsgen_amd.model: penalty losses {keys} are outside the rasterizer path this library replaces")
-        return self.mean.new_zeros(())
+        """trainer.py:469 -> :1114-1122: the weighted sum of the penalties configured under cfg.penalty -- alpha, mean, scale, NN,
+        compat, each weighted by schedule_value(<key>.value, step) and skipped at a weight <= 0 (scale: at 0).  NN and compat take
+        their neighbours from gsgen_amd.knn without autograd.  With a writer the reference's scalars are logged
+        (auxiliary/<key>_penalty, ..._weight, compat's effective_rate, total: each a host sync); without one nothing synchronises.
+        `move` and the pbr-only `specular` / `normal` raise NotImplementedError when weighted."""
+        loss = self.mean.new_zeros(())
+        for key in list(_get(self.cfg, "penalty", None) or []):
+            w = schedule_value(_get(self._penalty_node(key), "value", 0.0), step, None)
+            if key in self._PENALTY_UNSUPPORTED:
+                if w:
+                    raise NotImplementedError(f"gsgen_amd.model: penalty {key!r} {self._PENALTY_UNSUPPORTED[key]}")
+                continue
+            term = getattr(self, f"_penalty_{key}", None)
+            if term is None:
+                raise ValueError(f"gsgen_amd.model: no penalty named {key!r}")
+            if not (w != 0 if key == "scale" else w > 0):
+                continue
+            value, extra = term()
+            if writer is not None:
+                writer.add_scalar(f"auxiliary/{key}_penalty", value.item(), step)
+                for name, get in extra.items():
+                    writer.add_scalar(f"auxiliary/{name}", get(), step)
+                writer.add_scalar(f"auxiliary/{key}_penalty_weight", w, step)
+            loss = loss + w * value
+        if writer is not None:
+            writer.add_scalar("auxiliary/total", loss.item(), step)
+        return loss
 
     @torch.no_grad()
     def log(self, writer, step):

@@ -42,7 +42,7 @@ extern "C" {
 
 typedef void *gsgen_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
-#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4 */
+#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32 */
 #define GSGEN_EINVAL (-3)       /* null pointer / inconsistent sizes */
 #define GSGEN_EWORKSPACE (-4)   /* workspace too small */
 
@@ -716,6 +716,20 @@ int gsgen_vol_render_rgb_backward_batch(uint32_t n_views, const gsgen_rgbd_view 
                                         float *grad_alpha, uint32_t tile_size, uint32_t n_tiles_h,
                                         uint32_t n_tiles_w, uint32_t H, uint32_t W, float thresh,
                                         void *batch_workspace, gsgen_stream_t stream);
+
+/* ---- exact self k-nearest neighbours (gsgen_amd/csrc/knn.hip) --------------------------------------------------------
+ * replaces pytorch3d's knn_points as utils/ops.py:104-134 calls it (and faiss IndexFlatL2, utils/initialize.py:16-35).
+ * points [n_points,3] fp32; every point is also a query.  Row i of dist2 [n_points,K] fp32 / idx [n_points,K] int32 lists the K
+ * nearest points in ascending (dist2, index) order, dist2 = dx*dx + dy*dy + dz*dz with d = p_j - p_i evaluated left to right
+ * (an fp32 brute force reproduces every bit); row i holds i itself at distance 0, after any lower-index exact duplicate.
+ * A point with a NaN / Inf coordinate is nobody's neighbour; its own row, and every row with fewer than K finite candidates, is
+ * padded with idx -1, dist2 +inf.  K in 1..32 (else GSGEN_EUNSUPPORTED); n_points == 0 or K > n_points: GSGEN_EINVAL.
+ * workspace: device, gsgen_knn_workspace_bytes(n_points, K) bytes (0 for an unsupported pair).  Grid bounds and counts are
+ * computed on the device and the launch shapes depend on (n_points, K) alone: no host synchronisation, so the call can be
+ * captured in a hipGraph and replayed on new values of the same buffers. */
+size_t gsgen_knn_workspace_bytes(uint32_t n_points, uint32_t K);
+int gsgen_knn(const float *points, uint32_t n_points, uint32_t K, float *dist2, int32_t *idx, void *workspace,
+              size_t workspace_bytes, gsgen_stream_t stream);
 
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
