@@ -22,7 +22,7 @@ class ShView(C.Structure):
                 ("tile_order", vp), ("topleft", vp), ("c2w", vp), ("bg_rgb", vp),
                 ("pixel_size_x", f32), ("pixel_size_y", f32), ("out", vp), ("T", vp),
                 ("segment_workspace", vp), ("grad_out", vp), ("grad_mean", vp), ("grad_cov", vp), ("route_report", vp),
-                ("no_fallback", u32)]
+                ("no_fallback", u32), ("pixel_size_dev", vp)]
 
 
 class RgbdView(C.Structure):

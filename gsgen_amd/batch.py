@@ -332,8 +332,12 @@ class BatchRenderer:
         in the view tables, i.e. in kernel arguments too; True -- the compositing kernels read both from DEVICE memory (filled by one
         enqueue, upload_cameras), and a render enqueued while the stream is being captured uploads nothing: a
         captured hipGraph of a step (gsgen_amd.graph.CapturedStep) then replays for whatever cameras were uploaded before the
-        replay -- poses and intrinsics.  RGB + heads and RGB batches (render_heads, render with C = 0); SH batches keep their pixel
-        sizes in the view tables."""
+        replay -- poses and intrinsics.  Every kind of batch: RGB + heads and RGB (gsgen_rgbd_view::pixel_size_dev) and SH (render with
+        C > 0; gsgen_sh_view::pixel_size_dev, which selects the SH batches' device-pixel-size kernels -- the default
+        renderer's launches are untouched).  Such a renderer never sets no_fallback for an SH degree-3 batch: the two persistent exact
+        fallback launches are part of every step.  A replay cannot act on the crowded-tile report words (_route_mode is host code),
+        and a graph captured in "no fallback" mode could not bring the fallbacks back, so the mode that is at full speed on crowded
+        tiles is the one that is frozen -- eagerly too, so that a captured step and an eager one enqueue the same launches."""
         self.N, self.W, self.H, self.device = N, W, H, torch.device(device)
         self.device_cameras = bool(device_cameras)
         self.segments = int(segments)
@@ -531,6 +535,8 @@ class BatchRenderer:
             v.mean, v.cov, v.start, v.end, v.gaussian_ids = _p(buf.mean2d), _p(buf.cov2d), _p(buf.start), _p(buf.end), _p(buf.ids)
             v.tile_order = buf.tile_order()
             v.topleft = cam + 224
+            if self.device_cameras:
+                v.pixel_size_dev = self._pix.data_ptr() + 8 * i
             if kind == "sh":
                 v.c2w = cam + 232
                 v.segment_workspace = _p(buf.seg_ws) if self.segments > 1 else None
@@ -538,8 +544,6 @@ class BatchRenderer:
                 v.depth = _p(buf.depth)
                 if kind == "rgbd":
                     g.zero_grad_chan6 = v.grad_chan6 = c0 + st * i
-                if self.device_cameras:
-                    v.pixel_size_dev = self._pix.data_ptr() + 8 * i
         self._table_cache[kind] = (cap, geo, views)
         return geo, views
 
@@ -778,14 +782,14 @@ class BatchRenderer:
     def _route_mode(self):
         """-> (device address of the crowded-tile report word or None, no_fallback 0 | 1) for the batch about to be enqueued: reads and
         clears what earlier batches reported (plain host memory: no sync; an answer may be a batch or two late -- it is a hint, either
-        mode renders every tile correctly)"""
+        mode renders every tile correctly).  device_cameras renderers: never no_fallback (__init__)"""
         rep = self._route
         if rep.ptr(0) is None:
             return None, 0
         seen = int(rep._np[0, 0])
         rep._np[0, 0] = 0
         self._route_clean = 0 if seen else self._route_clean + 1
-        return rep.ptr(0), 1 if self._route_clean >= 3 else 0
+        return rep.ptr(0), 1 if (self._route_clean >= 3 and not self.device_cameras) else 0
 
     def _measure_bound(self, col):
         """renderer.sh_row_bounds_device into the renderer's own [N] floats (read by this batch's forward and backward only)"""
@@ -802,6 +806,13 @@ class BatchRenderer:
             _capi.load().sh_l1_bound_rows_running(self.N, col.data_ptr(), 4, self._smax.data_ptr(), self._rows.data_ptr(),
                                                   torch.cuda.current_stream(self.device).cuda_stream)
         return self._rows
+
+    def retighten_bound(self):
+        """zero the running maximum of the per-splat SH bounds on the current stream, so that the next measuring pass makes it tight
+        again: what _measure_bound does every 64th batch, for callers whose batches are replays of a captured graph (under capture the
+        re-zero is skipped: the maximum only ever rises there -- conservative, never wrong)"""
+        with _on(self.device):
+            self._smax.zero_()
 
     def render_heads(self, mean, qvec, svec, alpha, color, cam_infos, c2ws, bg_rgb=None, thresh=1e-4,
                      frustum_radius=6.0, tile_radius=6.0, detach_depth=True, stats=None, z_var=False, activations=None):

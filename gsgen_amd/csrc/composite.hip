@@ -985,6 +985,73 @@ k_composite_fwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
   }
 }
 
+// ---- pixel sizes from device memory (gsgen_sh_view::pixel_size_dev) --------------------------------------------------------------
+// The batched SH launches whose views carry the pointer run THESE kernels instead of k_composite_*_sh_vec<..., BATCH = true>: the same
+// three shapes (exact, polynomial, persistent exact fallback), the view's {psx, psy} taken from DEVICE memory -- two scalar loads per
+// workgroup, in front of every decision that depends on them (poly_route, the fallback's scan of the batch) -- and written into the
+// workgroup's own copy of the parameter block, from which the tile bodies take them as ever (pixel_coord, exact_tier_mask,
+// poly_tile_setup).  A captured hipGraph of such a launch replays for other intrinsics.  Kernels of their own, so that the ones every
+// launch without the pointer runs are what they were: no runtime test of the pointer in them (one was measured in round 6:
+// -0.25 .. -0.6 % on the headline, profiles/r06_notes.md section 21).
+struct PixelSizes { float x, y; };
+__device__ __forceinline__ PixelSizes view_pixel_sizes(const CompParams &v) {
+  const uniform_floats q = uniform_pointer(v.ps_dev);
+  return PixelSizes{q[0], q[1]};
+}
+__device__ __forceinline__ CompParams view_params_psd(const CompParams &v, const PixelSizes &ps) {
+  CompParams p = v;
+  p.psx = ps.x;
+  p.psy = ps.y;
+  return p;
+}
+template <int CB, int PPL, bool BATCH, int NB = 0, bool TRACK = true>  // (the template parameters of k_composite_fwd_sh_vec)
+__global__ void __launch_bounds__(256 / PPL)
+GS_WAVES_PER_EU((NB == kPolyNB && PPL == 4 && !TRACK) ? 5 : 1)  // (as k_composite_fwd_sh_vec)
+k_composite_fwd_psd_sh_vec(CompParams p_arg, ViewPack<true> pack) {
+  static_assert(BATCH && (NB == 0 || NB == kFallback || NB == kPolyNB), "the batched launches' three shapes");
+  const CompParams *plist = pack.table();
+  uint32_t bid = blockIdx.x;
+  if constexpr (NB == kFallback) {
+    static_assert(CB == 4, "the persistent exact fallback of a bounded batch");
+    __shared__ FwdShVecShared<4, false> sm;
+    const uint32_t B = (uint32_t)p_arg.n_lo, total = p_arg.vgrid;
+    const bool per_tile = plist[0].sh_rows != nullptr;  // (one mode per launch)
+    if (!per_tile) {
+      bool any = false;
+      for (uint32_t v = 0; v < B; ++v) {
+        const PixelSizes ps = view_pixel_sizes(plist[v]);
+        any |= !poly_route(plist[v].sh_bound, ps.x, ps.y);
+      }
+      if (!any) return;  // every view of the batch took the polynomial form
+    }
+    const uint32_t per = total / B;  // camera-major
+    uint32_t base = 0, view = 0;
+    for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
+      while (b >= base + per) { base += per; ++view; }
+      const CompParams *pp = &plist[view];
+      const PixelSizes ps = view_pixel_sizes(*pp);
+      if (per_tile ? !tile_flagged(*pp, b - base) : poly_route(pp->sh_bound, ps.x, ps.y)) continue;
+      const CompParams p = view_params_psd(*pp, ps);
+      composite_fwd_sh_vec_tile<4, PPL, 0, true>(p, b - base, sm);
+      __syncthreads();  // the LDS block is reused by the next tile
+    }
+  } else if constexpr (NB == kPolyNB) {
+    __shared__ FwdShVecShared<4, true> sm;
+    const CompParams *pp = &plist[batch_view(p_arg, bid)];
+    const PixelSizes ps = view_pixel_sizes(*pp);
+    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x, ps.y);
+    if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
+    CompParams p = view_params_psd(*pp, ps);
+    if (view_ok) p.sh_rows = nullptr;  // the whole scene is within this view's bound: no per-entry tests (tile_flags stay 0)
+    composite_fwd_sh_vec_tile<4, PPL, kPolyNB, false, TRACK>(p, bid, sm);
+  } else {
+    const CompParams *pp = &plist[batch_view(p_arg, bid)];
+    const CompParams p = view_params_psd(*pp, view_pixel_sizes(*pp));
+    __shared__ FwdShVecShared<CB, false> sm;
+    composite_fwd_sh_vec_tile<CB, PPL, 0>(p, bid, sm);
+  }
+}
+
 // ============================================================================================
 // backward
 // ============================================================================================
@@ -1763,6 +1830,56 @@ k_composite_bwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
   }
 }
 
+// pixel sizes from device memory: see k_composite_fwd_psd_sh_vec
+template <int CB, int PPL, bool BATCH, int NB = 0, bool MOM = false>  // (the template parameters of k_composite_bwd_sh_vec)
+__global__ void __launch_bounds__(64)
+GS_WAVES_PER_EU(NB == kPolyNB ? 4 : 1)  // (as k_composite_bwd_sh_vec)
+k_composite_bwd_psd_sh_vec(CompParams p_arg, ViewPack<true> pack) {
+  static_assert(PPL == 4 && BATCH && (NB == 0 || NB == kFallback || NB == kPolyNB), "the batched launches' three shapes");
+  const CompParams *plist = pack.table();
+  uint32_t bid = blockIdx.x, grid = gridDim.x;
+  if constexpr (NB == kFallback) {
+    static_assert(CB == 4, "the persistent exact fallback of a bounded batch");
+    __shared__ BwdShVecShared<4, 4, false> sm;
+    const uint32_t B = (uint32_t)p_arg.n_lo, total = p_arg.vgrid;
+    const bool per_tile = plist[0].sh_rows != nullptr;
+    if (!per_tile) {
+      bool any = false;
+      for (uint32_t v = 0; v < B; ++v) {
+        const PixelSizes ps = view_pixel_sizes(plist[v]);
+        any |= !poly_route(plist[v].sh_bound, ps.x, ps.y);
+      }
+      if (!any) return;
+    }
+    const uint32_t per = total / B;  // camera-major
+    const uint32_t tiles_grid = per / (uint32_t)(plist[0].nseg > 1 ? plist[0].nseg : 1);
+    uint32_t base = 0, view = 0;
+    for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
+      while (b >= base + per) { base += per; ++view; }
+      const CompParams *pp = &plist[view];
+      const PixelSizes ps = view_pixel_sizes(*pp);
+      if (per_tile ? !tile_flagged(*pp, (b - base) % tiles_grid) : poly_route(pp->sh_bound, ps.x, ps.y)) continue;
+      const CompParams p = view_params_psd(*pp, ps);
+      composite_bwd_sh_vec_tile<4, 4, 0, true, MOM>(p, b - base, per, sm);
+      __syncthreads();
+    }
+  } else if constexpr (NB == kPolyNB) {
+    __shared__ BwdShVecShared<4, 4, true> sm;
+    const CompParams *pp = &plist[batch_view(p_arg, bid, &grid)];
+    const PixelSizes ps = view_pixel_sizes(*pp);
+    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x, ps.y);
+    if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
+    CompParams p = view_params_psd(*pp, ps);
+    if (view_ok) p.sh_rows = nullptr;  // (as the forward: the same device value, the same decision)
+    composite_bwd_sh_vec_tile<4, 4, kPolyNB, false, MOM>(p, bid, grid, sm);
+  } else {
+    const CompParams *pp = &plist[batch_view(p_arg, bid, &grid)];
+    const CompParams p = view_params_psd(*pp, view_pixel_sizes(*pp));
+    __shared__ BwdShVecShared<CB, 4, false> sm;
+    composite_bwd_sh_vec_tile<CB, 4, 0, false, MOM>(p, bid, grid, sm);
+  }
+}
+
 // ============================================================================================
 // forward, post-activation channels, packed per-pixel arithmetic (batched RGB + heads)
 // ============================================================================================
@@ -2335,7 +2452,15 @@ static void for_each_chunk(const CompParams *host, uint32_t B, F &&f) {
     f(a, make_pack(host + b0, n), n);
   }
 }
-template <int CB>
+// PSD: the views carry gsgen_sh_view::pixel_size_dev -- the same launches, the device-pixel-size kernels (k_composite_*_psd_sh_vec)
+using ShBatchKernel = void (*)(CompParams, ViewPack<true>);
+template <bool PSD>
+static void launch_psd(ShBatchKernel plain, ShBatchKernel psd, dim3 grid, unsigned threads, hipStream_t s, const CompParams &p,
+                       const ViewPack<true> &plist) {
+  const ShBatchKernel k = PSD ? psd : plain;
+  hipLaunchKernelGGL(k, grid, dim3(threads), 0, s, p, plist);
+}
+template <int CB, bool PSD>
 static void launch_fwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &plist, uint32_t B, uint32_t nblk, hipStream_t s, bool bounded) {
   const dim3 g(nblk * B);
   if constexpr (CB == 4) {
@@ -2349,40 +2474,46 @@ static void launch_fwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &pl
       pf.vgrid = nblk * B;
       const uint32_t gf = pf.vgrid < 2560u ? pf.vgrid : 2560u;
       if (p0.sh_rows != nullptr) {  // per-tile routing: the polynomial kernel flags the tiles the fallback BEHIND it renders
-        if (p0.stop == nullptr) hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>), g, dim3(64), 0, s, p0, plist);
-        else hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB>), g, dim3(64), 0, s, p0, plist);
+        if (p0.stop == nullptr) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB, false>, g, 64, s, p0, plist);
+        else launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB>, g, 64, s, p0, plist);
         // (no_fallback: the caller's earlier batches reported no crowded tile -- nothing is handed over, nothing is launched)
-        if (!p0.no_fallback) hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 2, true, kFallback>), dim3(gf), dim3(128), 0, s, pf, plist);
+        if (!p0.no_fallback) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 2, true, kFallback>, k_composite_fwd_psd_sh_vec<4, 2, true, kFallback>, dim3(gf), 128, s, pf, plist);
         return;
       }
       launch_beside(
-          s, [&](hipStream_t q) { hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 2, true, kFallback>), dim3(gf), dim3(128), 0, q, pf, plist); },
+          s, [&](hipStream_t q) { launch_psd<PSD>(k_composite_fwd_sh_vec<4, 2, true, kFallback>, k_composite_fwd_psd_sh_vec<4, 2, true, kFallback>, dim3(gf), 128, q, pf, plist); },
           [&](hipStream_t q) {
-            if (p0.stop == nullptr) hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>), g, dim3(64), 0, q, p0, plist);
-            else hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB>), g, dim3(64), 0, q, p0, plist);
+            if (p0.stop == nullptr) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB, false>, g, 64, q, p0, plist);
+            else launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB>, g, 64, q, p0, plist);
           });
       return;
     }
   }
   // exact basis: packed, two wavefronts per tile (a lone 8-view launch is 4 % slower than at four but issues fewer vector
   // instructions, which is what counts with another batch's backward in flight: 3 010 vs 2 885 renders/s, round 2)
-  hipLaunchKernelGGL((k_composite_fwd_sh_vec<CB, 2, true>), g, dim3(128), 0, s, p0, plist);
+  launch_psd<PSD>(k_composite_fwd_sh_vec<CB, 2, true>, k_composite_fwd_psd_sh_vec<CB, 2, true>, g, 128, s, p0, plist);
 }
-int launch_fwd_sh_batch(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
+template <bool PSD>
+static int launch_fwd_sh_batch_p(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
   if (B == 0 || host[0].ntw * host[0].nth == 0) return 0;
   const uint32_t nblk = comp_grid(host[0]);
   const bool poly = C == 4 && bounded;
   for_each_chunk(host, B, [&](const CompParams &p0, const ViewPack<true> &pack, uint32_t n) {
     switch (C) {
-      case 1: launch_fwd_sh_batch_c<1>(p0, pack, n, nblk, s, false); break;
-      case 2: launch_fwd_sh_batch_c<2>(p0, pack, n, nblk, s, false); break;
-      case 3: launch_fwd_sh_batch_c<3>(p0, pack, n, nblk, s, false); break;
-      default: launch_fwd_sh_batch_c<4>(p0, pack, n, nblk, s, poly); break;
+      case 1: launch_fwd_sh_batch_c<1, PSD>(p0, pack, n, nblk, s, false); break;
+      case 2: launch_fwd_sh_batch_c<2, PSD>(p0, pack, n, nblk, s, false); break;
+      case 3: launch_fwd_sh_batch_c<3, PSD>(p0, pack, n, nblk, s, false); break;
+      default: launch_fwd_sh_batch_c<4, PSD>(p0, pack, n, nblk, s, poly); break;
     }
   });
   return (int)hipGetLastError();
 }
-template <int CB, bool MOM>
+// (fill_view_params: every view of a launch carries pixel_size_dev, or none does)
+int launch_fwd_sh_batch(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
+  return (B != 0 && host[0].ps_dev != nullptr) ? launch_fwd_sh_batch_p<true>(C, host, B, s, bounded)
+                                               : launch_fwd_sh_batch_p<false>(C, host, B, s, bounded);
+}
+template <int CB, bool MOM, bool PSD>
 static void launch_bwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &plist, uint32_t B, uint32_t nblk, hipStream_t s, bool bounded) {
   const dim3 g(nblk * B);
   if constexpr (CB == 4) {
@@ -2395,33 +2526,35 @@ static void launch_bwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &pl
       launch_beside(
           s, [&](hipStream_t q) {
             if (p0.sh_rows != nullptr && p0.no_fallback) return;  // (as the forward: no tile was handed over)
-            hipLaunchKernelGGL((k_composite_bwd_sh_vec<4, 4, true, kFallback, MOM>), dim3(gf), dim3(64), 0, q, pf, plist);
+            launch_psd<PSD>(k_composite_bwd_sh_vec<4, 4, true, kFallback, MOM>, k_composite_bwd_psd_sh_vec<4, 4, true, kFallback, MOM>, dim3(gf), 64, q, pf, plist);
           },
-          [&](hipStream_t q) { hipLaunchKernelGGL((k_composite_bwd_sh_vec<4, 4, true, kPolyNB, MOM>), g, dim3(64), 0, q, p0, plist); });
+          [&](hipStream_t q) { launch_psd<PSD>(k_composite_bwd_sh_vec<4, 4, true, kPolyNB, MOM>, k_composite_bwd_psd_sh_vec<4, 4, true, kPolyNB, MOM>, g, 64, q, p0, plist); });
       return;
     }
   }
   // one wavefront per tile: the per-Gaussian gradient reduction costs the same per wavefront whatever the number of pixels behind
   // it (two wavefronts per tile: 2 838 vs 3 492 renders/s on the exact basis, profiles/r04_ab_shapes.txt)
-  hipLaunchKernelGGL((k_composite_bwd_sh_vec<CB, 4, true, 0, MOM>), g, dim3(64), 0, s, p0, plist);
+  launch_psd<PSD>(k_composite_bwd_sh_vec<CB, 4, true, 0, MOM>, k_composite_bwd_psd_sh_vec<CB, 4, true, 0, MOM>, g, 64, s, p0, plist);
 }
-template <bool MOM>
+template <bool MOM, bool PSD>
 static int launch_bwd_sh_batch_m(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
   if (B == 0 || host[0].ntw * host[0].nth == 0) return 0;
   const uint32_t nblk = comp_grid(host[0]) * (uint32_t)(host[0].nseg > 1 ? host[0].nseg : 1);
   const bool poly = C == 4 && bounded;
   for_each_chunk(host, B, [&](const CompParams &p0, const ViewPack<true> &pack, uint32_t n) {
     switch (C) {
-      case 1: launch_bwd_sh_batch_c<1, MOM>(p0, pack, n, nblk, s, false); break;
-      case 2: launch_bwd_sh_batch_c<2, MOM>(p0, pack, n, nblk, s, false); break;
-      case 3: launch_bwd_sh_batch_c<3, MOM>(p0, pack, n, nblk, s, false); break;
-      default: launch_bwd_sh_batch_c<4, MOM>(p0, pack, n, nblk, s, poly); break;
+      case 1: launch_bwd_sh_batch_c<1, MOM, PSD>(p0, pack, n, nblk, s, false); break;
+      case 2: launch_bwd_sh_batch_c<2, MOM, PSD>(p0, pack, n, nblk, s, false); break;
+      case 3: launch_bwd_sh_batch_c<3, MOM, PSD>(p0, pack, n, nblk, s, false); break;
+      default: launch_bwd_sh_batch_c<4, MOM, PSD>(p0, pack, n, nblk, s, poly); break;
     }
   });
   return (int)hipGetLastError();
 }
 int launch_bwd_sh_batch(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded, bool moments = false) {
-  return moments ? launch_bwd_sh_batch_m<true>(C, host, B, s, bounded) : launch_bwd_sh_batch_m<false>(C, host, B, s, bounded);
+  if (B != 0 && host[0].ps_dev != nullptr)  // (as the forward)
+    return moments ? launch_bwd_sh_batch_m<true, true>(C, host, B, s, bounded) : launch_bwd_sh_batch_m<false, true>(C, host, B, s, bounded);
+  return moments ? launch_bwd_sh_batch_m<true, false>(C, host, B, s, bounded) : launch_bwd_sh_batch_m<false, false>(C, host, B, s, bounded);
 }
 
 // post-activation channels, B cameras per launch: packed, one wavefront per tile (the same operation sequence as the per-camera
@@ -2645,11 +2778,13 @@ static int fill_view_params(uint32_t n_views, const gsgen_sh_view *views, const 
     if ((v.tile_order == nullptr) != (views[0].tile_order == nullptr)) return GSGEN_EINVAL;
     if (n_segments > 1 && v.segment_workspace == nullptr) return GSGEN_EINVAL;
     if (backward && (!v.grad_out || !v.grad_mean || !v.grad_cov)) return GSGEN_EINVAL;
+    if ((v.pixel_size_dev == nullptr) != (views[0].pixel_size_dev == nullptr)) return GSGEN_EINVAL;  // one kernel variant per launch
     CompParams &p = ps[b];
     p.mean = v.mean; p.cov = v.cov; p.col = sh_coeffs; p.alpha = alpha;
     p.start = v.start; p.end = v.end; p.ids = v.gaussian_ids; p.topleft = v.topleft; p.rot = v.c2w;
     p.ntw = (int)ntw; p.nth = (int)nth; p.H = (int)H; p.W = (int)W;
     p.psx = v.pixel_size_x; p.psy = v.pixel_size_y; p.thresh = thresh;
+    p.ps_dev = v.pixel_size_dev;  // (set: the launch runs the k_composite_*_psd_sh_vec kernels, which ignore the two floats)
     p.tile_order = v.tile_order;
     p.n_hi = 0x7fffffff;
     p.sh_bound = sh_bound;  // (both given: the view's bound first -- a scene within it skips the per-entry tests --, then the rows)
@@ -2859,8 +2994,11 @@ int gsgen_sh_poly_applies(float sh_l1_bound, float max_pixel_size, uint32_t C) {
 // Host-side shortcut of a bounded batch: if NO view of the batch could take the polynomial form even for a coefficient bound as
 // small as 1/16 (very wide cameras: a tile's half diagonal beyond ~0.1 rad), the launch is the plain exact one -- full
 // occupancy, no polynomial kernel that every workgroup would leave, no persistent fallback.  (Exact is always right; forward and
-// backward of a batch apply the same rule to the same pixel sizes.)
+// backward of a batch apply the same rule to the same pixel sizes.)  Pixel sizes in device memory (gsgen_sh_view::pixel_size_dev) are
+// not the host's to test: such a batch always takes the bounded launches and every workgroup decides on the device -- a view that
+// is too wide leaves the polynomial kernel at once and is the persistent fallback's.
 static bool batch_can_be_polynomial(const std::vector<CompParams> &ps) {
+  if (!ps.empty() && ps[0].ps_dev != nullptr) return true;
   for (const CompParams &p : ps)
     if (poly_ok(1.0f / 16.0f, fmaxf(fabsf(p.psx), fabsf(p.psy)))) return true;
   return false;

@@ -18,7 +18,7 @@
         loss = cs(cam_infos, c2ws)                     # one copy + one graph launch; `loss` is the captured tensor, refilled
 
 What makes a replay render other cameras: a `device_cameras` renderer reads the camera blocks AND the pixel sizes from device memory
-(gsgen_rgbd_view::pixel_size_dev) -- nothing that changes from step to step is a kernel argument -- and uploads nothing while a stream
+(gsgen_rgbd_view::pixel_size_dev, gsgen_sh_view::pixel_size_dev) -- nothing that changes from step to step is a kernel argument -- and uploads nothing while a stream
 is being captured; `CapturedStep.__call__` uploads the new cameras (one small enqueue outside the graph) and replays.  Every camera must have the renderer's (W, H), and the batch the captured size.
 
 What a replay does NOT do is the host side of an eager call: the pair-list bookkeeping.  After every replay the renderer's report
@@ -28,7 +28,13 @@ moment ran on the old lists too and is settled with it), and whenever the lists 
 regrown -- quietly, with 25 % headroom left, or after an overflow -- the next call runs its step eagerly and records the graph again behind
 it (the lists' addresses are baked into a graph): one step per call either way.  Densify / prune change N: build a new renderer and a new CapturedStep.
 
-RGB + heads and RGB batches (render_heads; render with C = 0).  Reference: the loop this replaces is trainer.py:291-421 around
+Every batch kind: RGB + heads (render_heads), RGB (render with C = 0) and SH (render with C = 1..4, sh_basis "auto" or "exact": the SH kernels'
+device-pixel-size instantiations, selected by the renderer's view tables).  Two things about a captured SH degree-3 step with
+sh_basis="auto".  The routing mode is frozen with the graph, so a device_cameras renderer always enqueues the persistent exact
+fallback launches (never `no_fallback`): a replay cannot read the crowded-tile report words, and the mode that is always at full speed
+on crowded tiles is the one to freeze.  And the running maximum of the per-splat coefficient bounds, which the measuring pass inside the
+graph only ever raises, is zeroed by `__call__` outside the graph before every 64th replay -- the eager path's cadence -- so that the
+per-view shortcut stays tight over a long run.  Reference: the loop this replaces is trainer.py:291-421 around
 gs/gaussian_splatting.py:1423-1466."""
 import torch
 
@@ -63,6 +69,7 @@ class CapturedStep:
             if not getattr(o, "capturable", False):
                 raise ValueError("CapturedStep: optimizers must be FusedAdam(capturable=True)")
         self.replays = self.captures = 0
+        self._bound_every = 64  # replays between two re-zeroings of the renderer's running SH bound (BatchRenderer._measure_bound's cadence)
         self._capture(list(cam_infos), c2ws, self._warmup + 1)
 
     # ------------------------------------------------------------------------------------------------------------------------
@@ -113,6 +120,8 @@ class CapturedStep:
             self._model.prepare_replay({"camera_info": cam_infos, "c2w": c2ws})  # (a random background's colours for this replay)
         for o in self._optimizers:
             o.prepare_replay()
+        if self.replays % self._bound_every == 0:
+            br.retighten_bound()  # (the measuring pass inside the graph only raises the maximum: see the module docstring)
         self._graph.replay()
         self.replays += 1
         try:

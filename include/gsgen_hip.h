@@ -477,6 +477,15 @@ typedef struct gsgen_sh_view {
    *     meant for callers whose earlier batches reported none (gsgen_amd.BatchRenderer, bench.py: three clean reports in a row). */
   uint32_t *route_report;
   uint32_t no_fallback;
+  /* optional (zero = as before; every batched SH entry point, forward and backward): DEVICE address of {pixel_size_x, pixel_size_y} of
+   * this view, with the meaning of gsgen_rgbd_view::pixel_size_dev.  When set the kernels take the two from there -- once per
+   * workgroup, in front of their routing decisions -- and ignore the floats above: nothing that changes from step to step then travels
+   * in kernel arguments, so a captured hipGraph of an SH step can be replayed for other cameras (poses AND intrinsics: the reference
+   * samples a focal length per step, data/__init__.py:194) once their camera blocks and these floats are in place
+   * (gsgen_amd.graph.CapturedStep).  Set in every view of a launch or in none (GSGEN_EINVAL otherwise, nothing is enqueued): such a
+   * launch runs its own instantiations of the kernels, and the host-side shortcut of the bounded entry points ("no view of this batch
+   * can be polynomial: launch the exact kernels alone") is skipped -- the host does not know the floats; every workgroup decides. */
+  const float *pixel_size_dev;
 } gsgen_sh_view;
 size_t gsgen_sh_batch_workspace_bytes(uint32_t n_views);
 int gsgen_vol_render_sh_batch(uint32_t n_views, const gsgen_sh_view *views, uint32_t N,

@@ -35,13 +35,17 @@ ap.add_argument("--graph", action="store_true", help="replay the whole step from
 ap.add_argument("--profile", action="store_true", help="torch.profiler CPU table of 20 eager steps on stderr (where the host time goes)")
 ap.add_argument("--cprofile", action="store_true", help="cProfile of 200 eager steps on stderr (the Python side of the host time)")
 ap.add_argument("--pipeline", choices=["auto", "on", "off"], default="off", help="BatchRenderer(pipeline=...): two half-batches on two streams")
+ap.add_argument("--sh", action="store_true", help="SH degree 3 colours through BatchRenderer.render (C = 4, sh_basis='auto') instead of render_heads; "
+                                               "with --graph: a captured SH step (gsgen_sh_view::pixel_size_dev)")
 ap.add_argument("--torch-ops", action="store_true", help="activations / z_var as torch operations around render_heads (rounds 1-5) instead of inside its node")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-sc = scenes.pointe_scene(a.n, seed=0, C=1)
+sc = scenes.pointe_scene(a.n, seed=0, C=4 if a.sh else 1)
 logit = lambda x: np.log(x / (1 - x))  # noqa: E731
 raw0 = {"mean": sc["mean"], "qvec": sc["qvec"], "svec": np.log(sc["svec"]), "color": logit(np.clip(sc["color"], 1e-3, 1 - 1e-3)),
         "alpha": logit(np.clip(sc["alpha"], 1e-3, 1 - 1e-3))}
+if a.sh:  # the colour field is the SH coefficients [N,3,16] (their own activation is the kernels' sigmoid)
+    raw0["color"] = sc["sh"]
 opt = FusedAdam({k: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev) for k, v in raw0.items()},
                 {"mean": 5e-3, "qvec": 3e-3, "svec": 3e-3, "color": 1e-2, "alpha": 3e-3}, eps=1e-15,  # conf/base.yaml:8-30
                 capturable=a.graph)
@@ -67,6 +71,12 @@ def step(cis=None, c2ws=None):
         cis, c2ws = pool[tick[0] % len(pool)]
         tick[0] += 1
     opt.zero_grad()
+    if a.sh:  # rgb only: the SH path has no heads
+        rgb, _ = br.render(P["mean"], P["qvec"], torch.exp(P["svec"]), torch.sigmoid(P["alpha"]), P["color"], cis, c2ws, C=4, bg_rgb=bg,
+                           stats=stats)
+        (rgb * g_sds).sum().backward()
+        opt.step()
+        return
     if a.torch_ops:  # rounds 1-5: the activations, the background and z_var as torch kernels / autograd nodes around the launches
         rgb, dpt, opa, z2, _ = br.render_heads(P["mean"], P["qvec"], torch.exp(P["svec"]), torch.sigmoid(P["alpha"]),
                                                torch.sigmoid(P["color"]), cis, c2ws, bg_rgb=bg, stats=stats)
@@ -132,6 +142,7 @@ print(json.dumps({"metric": "optimisation-step iters/sec, renderer + optimiser s
                   "unit": "iters/s", "ms_per_iter": 1e3 * t1 / a.steps, "host_ms_per_iter": 1e3 * t_host / a.steps,
                   "views_per_s": a.batch * a.steps / t1, "hipgraph": bool(a.graph) and graph_error is None,
                   "cameras": "a fresh batch per step (pose and focal length)", "graph_captures": (cs.captures if a.graph and graph_error is None else None), "pipeline": a.pipeline, "hipgraph_error": graph_error,
+                  "colours": "SH degree 3 (render, C = 4)" if a.sh else "post-activation rgb + heads (render_heads)",
                   "config": {"workload": "BASELINE configs[4] without the diffusion model: 100k Gaussians, "
-                                         f"{a.batch} views at {a.res}x{a.res}, rgb + depth + opacity + z_var, "
+                                         f"{a.batch} views at {a.res}x{a.res}, " + ("rgb from SH degree 3, " if a.sh else "rgb + depth + opacity + z_var, ") +
                                          "densify statistics, Adam on the five raw fields", "gaussians": a.n}}))
