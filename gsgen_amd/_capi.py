@@ -95,6 +95,7 @@ SIGNATURES = {
     "gsgen_densify_update": [u32, vp, vp, vp, vp, vp, vp, vp],
     "gsgen_tile_culling_aabb_count": [u32, vp, vp, u32, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp, vp],
     "gsgen_selftest_reduce_scatter": [u32, vp, vp, vp],
+    "gsgen_selftest_reduce_scatter_sep16": [vp, vp, vp, vp],
     "gsgen_vol_render_rgbd": [u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, f32, f32, u32, u32,
                               f32, vp, vp, vp],
     "gsgen_vol_render_rgbd_backward": [u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32,

@@ -756,6 +756,18 @@ __global__ void __launch_bounds__(64) k_selftest_reduce_scatter(const float *__r
   out[64 + lane] = (float)(scatter_owner<P>(lane) ? scatter_comp<P>(lane) : -1);
 }
 
+// in [64 lanes, 16 components]: lane l's c[k] = (in[l][2 k], in[l][2 k + 1]); u [64 lanes]
+__global__ void __launch_bounds__(64) k_selftest_reduce_scatter_sep16(const float *__restrict__ in, const float *__restrict__ u,
+                                                                      float *__restrict__ out) {
+  v2f c[8];
+  const int lane = lane_id();
+#pragma unroll
+  for (int k = 0; k < 8; ++k) c[k] = v2f{in[lane * 16 + 2 * k], in[lane * 16 + 2 * k + 1]};
+  out[lane] = wave_reduce_scatter_sep16(c, u[lane]);
+  out[64 + lane] = (float)(sep16_owner(lane) ? sep16_comp(lane) : -1);
+  out[128 + lane] = (float)sep16_comp(lane);
+}
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct BinWs {
@@ -859,6 +871,13 @@ int gsgen_selftest_reduce_scatter(uint32_t P, const float *in /*[64,P]*/, float 
     case 64: hipLaunchKernelGGL((k_selftest_reduce_scatter<64>), dim3(1), dim3(64), 0, s, in, out); break;
     default: return GSGEN_EUNSUPPORTED;
   }
+  return (int)hipGetLastError();
+}
+
+int gsgen_selftest_reduce_scatter_sep16(const float *in /*[64,16]*/, const float *u /*[64]*/, float *out /*[192]*/,
+                                        gsgen_stream_t stream) {
+  if (in == nullptr || u == nullptr || out == nullptr) return GSGEN_EINVAL;
+  hipLaunchKernelGGL(k_selftest_reduce_scatter_sep16, dim3(1), dim3(64), 0, (hipStream_t)stream, in, u, out);
   return (int)hipGetLastError();
 }
 

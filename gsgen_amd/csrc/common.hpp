@@ -342,6 +342,39 @@ __device__ __forceinline__ bool scatter10_owner(int lane) {
   return (lane & 8) ? (lane & (16 | 4)) == 0 : true;
 }
 
+// SEPARABLE reduce-scatter of sixteen components (the polynomial SH backward: a 16 x 16 tile on one wavefront, lane = 16 * row + column,
+// so the lanes at distances 32 and 16 share their column and with it the column offset u).  Sums over such lanes commute with
+// multiplying by u: the two cross-row levels carry only what does not depend on u, the products are formed once on the row sums.
+//   stage A  c[2 k], c[2 k + 1] = the four values (v0, v1), (v2, v3) of class k = lane >> 4; distances 32 and 16 (6 packed
+//            exchanges): every lane holds its class's four values summed over the four lanes of its column;
+//   expand   to eight slots (v0, v1 | u v0, v2 | u v1, u^2 v0 | v3, -) -- classes 0..2: a channel's row sums (G0, G1, G2) of the
+//            weights against (1, v, v^2) become its six monomial moments in the order (1, v, u, v^2, uv, u^2), v3 rides along;
+//            class 3 takes u = 0: (v0, v1 | 0, v2 | 0, 0 | v3, -), its values pass through; slot 7 is dead (it ends as a copy of
+//            part of slot 3);
+//   stage B  distances 8, 4, 2 halve the eight slots, distance 1 is an all-reduce step.
+// Returns the wave-wide total of slot sep16_comp(lane) = 8 * class + slot; every slot sits in the two lanes of a pair,
+// sep16_owner(lane) marks the even one of each of the 24 live slots (3 x 7 + class 3's slots 0, 1, 3).
+__device__ __forceinline__ int sep16_comp(int lane) { return (lane >> 4) * 8 + ((lane >> 1) & 7); }
+__device__ __forceinline__ bool sep16_live(int comp) {
+  const int slot = comp & 7;
+  return (comp >> 3) < 3 ? slot < 7 : (slot == 0 || slot == 1 || slot == 3);
+}
+__device__ __forceinline__ bool sep16_owner(int lane) { return (lane & 1) == 0 && sep16_live(sep16_comp(lane)); }
+__device__ __forceinline__ float wave_reduce_scatter_sep16(v2f (&c)[8], float u) {
+  const v2f a0 = xchg_add2<32>(c[0], c[4]), a1 = xchg_add2<32>(c[1], c[5]);  // lanes < 32: classes 0, 1 | lanes >= 32: 2, 3
+  const v2f a2 = xchg_add2<32>(c[2], c[6]), a3 = xchg_add2<32>(c[3], c[7]);
+  const v2f b0 = xchg_add2<16>(a0, a2), b1 = xchg_add2<16>(a1, a3);          // (v0, v1), (v2, v3) of the lane's class
+  const float ue = (lane_id() & 48) == 48 ? 0.0f : u;
+  const float uv0 = ue * b0[0];
+  // (per register, on the fused v_add_f32_dpp pairs of xchg_add_row: the packed form xchg_add2<8 | 4> is four DPP moves, their
+  // copies of the old operand and a packed add -- 24 instructions for these two levels in the entry loop's ISA against 12)
+  const float f0 = xchg_any<8>(b0[0], ue * b0[1]), f1 = xchg_any<8>(b0[1], ue * uv0);  // bit 8 clear: slots 0..3, set: 4..7
+  const float f2 = xchg_any<8>(uv0, b1[1]), f3 = xchg_any<8>(b1[0], b1[0]);            // (slot 7 is dead: no zero register)
+  const v2f g = {xchg_any<4>(f0, f2), xchg_any<4>(f1, f3)};
+  const float q = xchg_any<2>(g[0], g[1]);
+  return xchg_any<1>(q, q);
+}
+
 // Only the log2(P) halving levels: every lane ends with the partial sum of component
 // scatter_comp<P>(lane) over the lanes that agree with it on the remaining lane bits (64 / P
 // partials per component, to be combined by the caller -- e.g. by the atomics that follow anyway).

@@ -1311,7 +1311,9 @@ k_composite_bwd_pixel(CompParams p) {
 // form, `CHRED = false`, is in the history up to round 3).
 // NB > 0 (= kPolyNB; SH degree 3, one wavefront per tile): the tile-local polynomial form of the per-pixel basis
 // (composite_common.hpp) -- 6-term contractions, 3 x 6 SH gradient components across the lanes, expanded by the tile's V
-// (through 24 floats of LDS) in front of the 48 atomics.
+// (through 24 floats of LDS) in front of the 48 atomics.  Its reduction is ONE separable reduce-scatter per entry (rows before
+// columns, wave_reduce_scatter_sep16: 9 row sums + 6 geometric values cross the rows, the column offset multiplies the sums), not the
+// channel-by-channel form above: 193 -> 179 vector instructions in the moment form's entry loop, 208 -> 194 in the plain form's.
 // NB = kRouted: as k_composite_fwd_sh_vec -- one launch, the form chosen per workgroup from the device-resident bound.
 template <int CB, int PPL, bool POLY>
 struct BwdShVecShared {
@@ -1410,16 +1412,21 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
     static_assert(!POLY || KB * 3 * kPolyNB >= kPolyNodes * 16, "node scratch fits the coefficient buffer");
     poly_tile_setup<NT>(p, tx, ty, Ws, Vs);
     {
-      // lane (m, slot e = comp - 6) -> m 0: mean[e] | 1: cov[e] | 2: cov[3], alpha | 3: -, cov[2]
-      const int m = lane & 3, e = scatter_comp<8>(lane) - 6;
-      if constexpr (MOM) {  // m 0: (Mx, My) -> mean[e] | 1: (Mxx, Mxy) -> cov[e] | 2: (Myy, alpha) -> cov[2], alpha | 3: -
-        if (scatter_rows_owner<8>(lane) && e >= 0 && m < 3) {
-          geo_base = m == 0 ? p.g_mean + e : (m == 1 ? p.g_cov + e : (e == 0 ? p.g_cov + 2 : p.g_alpha));
-          geo_stride = m == 0 ? 2u : ((m == 2 && e == 1) ? 1u : 4u);
+      // the lane's geometric slot in wave_reduce_scatter_sep16's layout: slot 6 of class 0 | 1 | 2 = mean[0] | cov[0] | cov[3] (MOM:
+      // Myy -> cov[2]); class 3: slot 0 = mean[1], 1 = cov[1], 3 = alpha.  Every slot ends in both lanes of a pair: the plain form's
+      // grad_cov[2] = grad_cov[1] is the atomic of the pair's second lane (the moment form leaves it to the projection backward)
+      const int comp = sep16_comp(lane), cls = comp >> 3, slot = comp & 7;
+      if (sep16_owner(lane)) {
+        if (cls < 3 && slot == 6) {
+          geo_base = cls == 0 ? p.g_mean : p.g_cov + (cls == 1 ? 0 : (MOM ? 2 : 3));
+          geo_stride = cls == 0 ? 2u : 4u;
+        } else if (cls == 3) {
+          geo_base = slot == 0 ? p.g_mean + 1 : (slot == 1 ? p.g_cov + 1 : p.g_alpha);
+          geo_stride = slot == 0 ? 2u : (slot == 1 ? 4u : 1u);
         }
-      } else if (scatter_rows_owner<8>(lane) && e >= 0 && !(m == 3 && e == 0)) {
-        geo_base = m == 0 ? p.g_mean + e : ((m == 2 && e == 1) ? p.g_alpha : p.g_cov + (m == 1 ? e : (m == 2 ? 3 : 2)));
-        geo_stride = m == 0 ? 2u : ((m == 2 && e == 1) ? 1u : 4u);
+      } else if (!MOM && cls == 3 && slot == 1) {  // (lane & 1: the second holder of Mxy's slot)
+        geo_base = p.g_cov + 2;
+        geo_stride = 4u;
       }
     }
   } else {
@@ -1551,7 +1558,7 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
       constexpr int PCH = CCP <= 2 ? 2 : (CCP <= 4 ? 4 : (CCP <= 8 ? 8 : 16));  // one channel's components in its reduction
       float chsum[3] = {0.0f, 0.0f, 0.0f};
       const float *cg = POLY ? &Ws[g * 3 * kPolyStride] : &S.col[g * TR::NCOLP];
-      v2f pch[POLY ? 3 : 1][3];  // POLY: the channels' six components each, reduced after the geometric part
+      float rs[POLY ? 3 : 1][3];  // POLY: the channels' row sums (G0, G1, G2), reduced after the geometric part
       v2f w2[NP], inv1m2[NP], pAG2[NP];
 #pragma unroll
       for (int jp = 0; jp < NP; ++jp) {
@@ -1607,10 +1614,8 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
             if (jp == 0) { g0 = gs; g1 = gs * pv2[jp]; g2 = gs * pvsq2[jp]; }
             else { g0 = g0 + gs; g1 = fma2(gs, pv2[jp], g1); g2 = fma2(gs, pvsq2[jp], g2); }
           }
-          const float G0 = add_scalar(g0[0], g0[1]), G1 = add_scalar(g1[0], g1[1]), G2s = add_scalar(g2[0], g2[1]);
-          const float uG0 = pu * G0;
-          // (1, v, u, v^2, uv, u^2): six of the channel's eight reduction slots; the last two carry geometric components (below)
-          pch[c][0] = v2f{G0, G1}; pch[c][1] = v2f{uG0, G2s}; pch[c][2] = v2f{pu * G1, pu * uG0};
+          // (the column's u multiplies them behind the cross-row levels of the reduction: wave_reduce_scatter_sep16)
+          rs[c][0] = add_scalar(g0[0], g0[1]); rs[c][1] = add_scalar(g1[0], g1[1]); rs[c][2] = add_scalar(g2[0], g2[1]);
         }
 #pragma unroll
         for (int jp = 0; jp < NP; ++jp) {
@@ -1707,22 +1712,18 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
       const float c0 = gc0[0] + gc0[1], c1 = gc1[0] + gc1[1], c3 = gc3[0] + gc3[1];
       const float ga = gal[0] + gal[1];
       if constexpr (POLY) {
-        // The six DISTINCT geometric components (grad_cov[1] and grad_cov[2] receive the same value, kernels.h:414-415) ride
-        // in the two spare slots of the three channels' 8-wide reductions: (m0, m1) | (c0, c1) | (c3, alpha).  No fourth
-        // reduction (363 -> 348 vector instructions per (wavefront, entry) when it went in; 321 now).
-        v2f t0[4] = {pch[0][0], pch[0][1], pch[0][2], v2f{m0, m1}};
-        v2f t1[4] = {pch[1][0], pch[1][1], pch[1][2], v2f{c0, c1}};
-        v2f t2[4] = {pch[2][0], pch[2][1], pch[2][2], v2f{c3, ga}};
-        const float s0 = wave_reduce_scatter2_rows<8>(t0), s1 = wave_reduce_scatter2_rows<8>(t1), s2 = wave_reduce_scatter2_rows<8>(t2);
-        // (the fourth quad lane receives channel 1's vector again: its (c0, c1) slot pays for grad_cov[2] = grad_cov[1])
-        const float tot = quad_reduce_scatter4(s0, s1, s2, s1);
-        const int m = lane & 3;  // the vector this lane ends up with: channel 0 / 1 / 2 / 1 again
-        const int comp = scatter_comp<8>(lane);
-        const bool owner = scatter_rows_owner<8>(lane);
+        // Rows before columns (wave_reduce_scatter_sep16): the lanes at distances 32 and 16 share their column, so the channels' row
+        // sums and the six DISTINCT geometric components (grad_cov[1] and grad_cov[2] receive the same value, kernels.h:414-415)
+        // cross the rows as 15 values -- class c = channel c's (G0, G1, G2) + one geometric value, class 3 the other three -- and
+        // the column's u enters once, on the row sums: slots (1, v, u, v^2, uv, u^2 | geometric) per channel.
+        v2f t8[8] = {v2f{rs[0][0], rs[0][1]}, v2f{rs[0][2], m0}, v2f{rs[1][0], rs[1][1]}, v2f{rs[1][2], c0},
+                     v2f{rs[2][0], rs[2][1]}, v2f{rs[2][2], c3}, v2f{m1, c1}, v2f{ga, 0.0f}};
+        const float tot = wave_reduce_scatter_sep16(t8, pu);
+        const int comp = sep16_comp(lane);  // 8 * (channel, or 3 for the geometric class) + slot
         const size_t id = (size_t)S.id[g];
         // d L / d sh[c][k] = sum_r gw[c][r] V[r][k]: the 18 reduced values go through LDS, lanes (c, k) = (lane / 16,
         // lane % 16) expand them with their column of V (one wavefront per workgroup: the barrier is a wait)
-        if (owner && m < 3 && comp < kPolyNB) gw_s[m * 8 + comp] = tot;
+        if (sep16_owner(lane) && comp < 3 * 8 && (comp & 7) < kPolyNB) gw_s[comp] = tot;
         // the geometric components, ONE atomic instruction (geo_base / geo_stride: the lane's slot, fixed before the loop)
         if (geo_base != nullptr) atomicAdd(geo_base + id * geo_stride, tot);
         __syncthreads();

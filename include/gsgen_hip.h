@@ -745,6 +745,13 @@ int gsgen_knn(const float *points, uint32_t n_points, uint32_t K, float *dist2, 
  * lane owns (-1: duplicate holder); P in {8,16,32,64}. */
 int gsgen_selftest_reduce_scatter(uint32_t P, const float *in, float *out, gsgen_stream_t stream);
 
+/* Self test of the separable 16-component reduce-scatter of the polynomial SH backward (tests only): in [64 lanes, 16 components]
+ * (class k = lane / 16 keeps components 4 k .. 4 k + 3 = v0 .. v3), u [64 lanes] (equal for lanes that agree modulo 16);
+ * out[0..64) = per-lane result, out[64..128) = the slot 8 * class + slot that lane owns (-1: none: second holder or a dead slot),
+ * out[128..192) = the slot the lane's result belongs to.  Slots of classes 0..2: v0, v1, u v0, v2, u v1, u^2 v0, v3, -; of class 3:
+ * v0, v1, 0, v2, 0, 0, v3, - (the kernel pads v3). */
+int gsgen_selftest_reduce_scatter_sep16(const float *in, const float *u, float *out, gsgen_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
