@@ -26,6 +26,16 @@
 //      outlier list only when the box's nearest face is within its K-th distance; an outlier query reads the outlier list first
 //      and the grid only while the box is within its K-th distance.  Every bound is shrunk by a margin that covers the rounding
 //      of the cell assignment, so pruning never drops a candidate that could enter the list.
+//
+// Steps 1-3 are the INDEX over `points` (build_index); step 4 is one of three consumers of it:
+//   k_knn_query       every point is a query (gsgen_knn, above).
+//   k_knn_query_ext   queries from an array of their own, in the caller's order (gsgen_knn_query): d = p_j - q.  The query's cell
+//                     comes from the index's Params; a query outside the grid box takes the outlier-query path, a non-finite
+//                     query keeps its padded row.
+//   k_density_grid    the lattice of utils/export.py:66-120 (get_density_val_grid_from_ckpt): a wavefront takes a 4 x 4 x 4 brick of
+//                     lattice points, runs the same search and sums opacity_j exp(-1/2 d^T Sigma_j^-1 d) over the neighbours it
+//                     keeps, straight from the top-K in registers: one store per lattice point, no idx / dist2 in memory.
+//                     Sigma^-1 = R diag(1 / s^2) R^T in closed form, once per Gaussian (k_density_prep).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -467,6 +477,128 @@ __global__ void __launch_bounds__(kBlock) k_knn_query(uint32_t N, uint32_t K, ui
   }
 }
 
+// --- 4b. queries that are not points of the index ------------------------------------------------------------------------
+// The search of k_knn_query for any position q: in the grid box (the test k_knn_count applies to a point) the grid, then the
+// outliers if the box's exterior is nearer than the K-th distance; outside it the outliers first, then the grid with the distance
+// to the box as a floor.  A non-finite q searches nothing: its list stays padded.
+template <int L>
+__device__ __forceinline__ void search_ext(unsigned long long (&list)[L], uint32_t cap, const Params *__restrict__ P,
+                                           const uint32_t *__restrict__ start, const float4 *__restrict__ sorted, const float4 q) {
+  if (!finite3(q.x, q.y, q.z)) return;
+  const uint32_t o_begin = start[cap], o_end = start[cap + 1];
+  const float qv[3] = {q.x, q.y, q.z};
+  const bool inbox = q.x >= P->lo[0] && q.x <= P->hi[0] && q.y >= P->lo[1] && q.y <= P->hi[1] && q.z >= P->lo[2] && q.z <= P->hi[2];
+  if (inbox) {
+    scan_grid<L>(list, P, start, sorted, q, 0.0f);
+    if (o_end > o_begin) {
+      float ext = 3.402823466e38f;
+      for (int a = 0; a < 3; ++a) {
+        const float m = 1e-6f * (fabsf(P->lo[a]) + fabsf(P->hi[a]) + fabsf(qv[a]));
+        ext = fminf(ext, fmaxf(fminf(qv[a] - P->lo[a], P->hi[a] - qv[a]) - m, 0.0f));
+      }
+      if (ext * ext <= kth_of(list[L - 1])) scan_range<L>(list, sorted, o_begin, o_end, q);
+    }
+  } else {
+    scan_range<L>(list, sorted, o_begin, o_end, q);
+    float g2 = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+      const float m = 1e-6f * (fabsf(P->lo[a]) + fabsf(P->hi[a]) + fabsf(qv[a]));
+      const float g = axis_gap(qv[a], P->lo[a], P->hi[a], m);
+      g2 += g * g;
+    }
+    scan_grid<L>(list, P, start, sorted, q, sqrtf(g2));
+  }
+}
+
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_knn_query_ext(uint32_t Q, uint32_t K, uint32_t cap, const Params *__restrict__ P,
+                                                           const uint32_t *__restrict__ start, const float4 *__restrict__ sorted,
+                                                           const float *__restrict__ queries, float *__restrict__ dist2,
+                                                           int32_t *__restrict__ idx) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= Q) return;
+  const float4 q = make_float4(queries[3 * (size_t)t], queries[3 * (size_t)t + 1], queries[3 * (size_t)t + 2], 0.0f);
+  unsigned long long list[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) list[k] = kPad;
+  search_ext<L>(list, cap, P, start, sorted, q);
+  float *drow = dist2 + (size_t)t * K;
+  int32_t *irow = idx + (size_t)t * K;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    if ((uint32_t)k < K) {
+      const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+      drow[k] = __uint_as_float((uint32_t)(list[k] >> 32));
+      irow[k] = j == 0xffffffffu ? -1 : (int32_t)j;
+    }
+  }
+}
+
+// --- 4c. the density lattice ---------------------------------------------------------------------------------------------
+// rec[2 i] = (a00, a01, a02, a11), rec[2 i + 1] = (a12, a22, opacity, 0): A = Sigma^-1 = R diag(1 / s^2) R^T, R the rotation of
+// geometry.hip's quat_to_rot (kornia 0.6.0, w first, normalised with eps 1e-12), Sigma = R diag(s^2) R^T as qsvec2covmat_batched
+// builds it.  A_ij = (R_i0 R_j0) w_0 + (R_i1 R_j1) w_1 + (R_i2 R_j2) w_2, w_k = 1 / (s_k s_k), left to right.
+__global__ void __launch_bounds__(kBlock) k_density_prep(uint32_t N, const float *__restrict__ qvec, const float *__restrict__ scale,
+                                                          const float *__restrict__ opacity, float4 *__restrict__ rec) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const float *q = qvec + 4 * (size_t)i, *sc = scale + 3 * (size_t)i;
+  float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  n = fmaxf(n, 1e-12f);
+  const float w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
+  const float tx = 2.0f * x, ty = 2.0f * y, tz = 2.0f * z;
+  const float twx = tx * w, twy = ty * w, twz = tz * w;
+  const float txx = tx * x, txy = ty * x, txz = tz * x;
+  const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  const float R[3][3] = {{1.0f - (tyy + tzz), txy - twz, txz + twy},
+                         {txy + twz, 1.0f - (txx + tzz), tyz - twx},
+                         {txz - twy, tyz + twx, 1.0f - (txx + tyy)}};
+  const float w0 = 1.0f / (sc[0] * sc[0]), w1 = 1.0f / (sc[1] * sc[1]), w2 = 1.0f / (sc[2] * sc[2]);
+  float A[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = a; b < 3; ++b) A[a][b] = R[a][0] * R[b][0] * w0 + R[a][1] * R[b][1] * w1 + R[a][2] * R[b][2] * w2;
+  rec[2 * (size_t)i] = make_float4(A[0][0], A[0][1], A[0][2], A[1][1]);
+  rec[2 * (size_t)i + 1] = make_float4(A[1][2], A[2][2], opacity[i], 0.0f);
+}
+
+// A 256-thread workgroup = four wavefronts = four 4 x 4 x 4 bricks (z fastest, as the output is laid out); lanes past nx, ny or nz
+// idle.  Kept neighbours: entries skip .. skip + K - 1 of the sorted list; a padded entry (index -1) contributes nothing.
+// m = a00 dx dx + a11 dy dy + a22 dz dz + 2 (a01 dx dy + a02 dx dz + a12 dy dz), d = q - mean_j, every product left to right.
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_density_grid(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t K, uint32_t skip, uint32_t cap,
+                                                          const Params *__restrict__ P, const uint32_t *__restrict__ start,
+                                                          const float4 *__restrict__ sorted, const float *__restrict__ mean,
+                                                          const float4 *__restrict__ rec, const float *__restrict__ axis_x,
+                                                          const float *__restrict__ axis_y, const float *__restrict__ axis_z,
+                                                          float *__restrict__ out) {
+  const uint32_t by = (ny + 3) / 4, bz = (nz + 3) / 4;
+  const uint32_t brick = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const uint32_t ix = (brick / (by * bz)) * 4 + (lane >> 4), iy = ((brick / bz) % by) * 4 + ((lane >> 2) & 3),
+                 iz = (brick % bz) * 4 + (lane & 3);
+  if (ix >= nx || iy >= ny || iz >= nz) return;
+  const float4 q = make_float4(axis_x[ix], axis_y[iy], axis_z[iz], 0.0f);
+  unsigned long long list[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) list[k] = kPad;
+  search_ext<L>(list, cap, P, start, sorted, q);
+  float sum = 0.0f;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+    if ((uint32_t)k >= skip && (uint32_t)k < K + skip && j != 0xffffffffu) {
+      const float4 r0 = rec[2 * (size_t)j], r1 = rec[2 * (size_t)j + 1];
+      const float dx = q.x - mean[3 * (size_t)j], dy = q.y - mean[3 * (size_t)j + 1], dz = q.z - mean[3 * (size_t)j + 2];
+      const float diag = r0.x * dx * dx + r0.w * dy * dy + r1.y * dz * dz;
+      const float off = r0.y * dx * dy + r0.z * dx * dz + r1.x * dy * dz;
+      const float m = diag + 2.0f * off;
+      sum += r1.z * expf(-0.5f * m);
+    }
+  }
+  out[((size_t)ix * ny + iy) * nz + iz] = sum;
+}
+
 // --- workspace --------------------------------------------------------------------------------------------------------
 struct Ws {
   Params *P;
@@ -503,6 +635,45 @@ inline void launch_query(uint32_t N, uint32_t K, uint32_t cap, const Ws &w, floa
                      (const uint32_t *)w.start, (const float4 *)w.sorted, dist2, idx);
 }
 
+template <int L>
+inline void launch_query_ext(uint32_t Q, uint32_t K, uint32_t cap, const Ws &w, const float *queries, float *dist2, int32_t *idx,
+                             hipStream_t s) {
+  hipLaunchKernelGGL((k_knn_query_ext<L>), dim3((Q + kBlock - 1) / kBlock), dim3(kBlock), 0, s, Q, K, cap, (const Params *)w.P,
+                     (const uint32_t *)w.start, (const float4 *)w.sorted, queries, dist2, idx);
+}
+
+template <int L>
+inline void launch_density(uint32_t blocks, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t K, uint32_t skip, uint32_t cap, const Ws &w,
+                           const float *mean, const float4 *rec, const float *ax, const float *ay, const float *az, float *out,
+                           hipStream_t s) {
+  hipLaunchKernelGGL((k_density_grid<L>), dim3(blocks), dim3(kBlock), 0, s, nx, ny, nz, K, skip, cap, (const Params *)w.P,
+                     (const uint32_t *)w.start, (const float4 *)w.sorted, mean, rec, ax, ay, az, out);
+}
+
+// steps 1-3: the index over `points` (launch shapes from N and K alone)
+inline int build_index(const float *points, uint32_t N, uint32_t K, const Ws &w, hipStream_t s) {
+  const uint32_t cap = cell_cap(N, K), M = cap + 3, T = (M + kScanTile - 1) / kScanTile;
+  const uint32_t nb = reduce_blocks(N), ng = (N + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_knn_bbox, dim3(nb), dim3(kBlock), 0, s, N, points, w.part);
+  hipLaunchKernelGGL(k_knn_bbox_final, dim3(1), dim3(64), 0, s, nb, (const float *)w.part, w.P);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (int e = (int)hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * 3 * kBins, s)) return e;
+    hipLaunchKernelGGL(k_knn_hist, dim3(nb), dim3(kBlock), 0, s, N, points, (const Params *)w.P, w.hist);
+    hipLaunchKernelGGL(k_knn_select, dim3(1), dim3(192), 0, s, (const uint32_t *)w.hist, w.P, cap, pass);
+  }
+  if (int e = (int)hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * (size_t)M, s)) return e;
+  hipLaunchKernelGGL(k_knn_count, dim3(ng), dim3(kBlock), 0, s, N, cap, points, (const Params *)w.P, w.cell_of, w.counts);
+  hipLaunchKernelGGL(k_knn_scan_tiles, dim3(T), dim3(kBlock), 0, s, M, (const uint32_t *)w.counts, w.tile_sum);
+  hipLaunchKernelGGL(k_knn_scan_sums, dim3(1), dim3(kBlock), 0, s, T, w.tile_sum);
+  hipLaunchKernelGGL(k_knn_scan_apply, dim3(T), dim3(kBlock), 0, s, M, (const uint32_t *)w.counts, (const uint32_t *)w.tile_sum,
+                     w.start, w.cursor);
+  hipLaunchKernelGGL(k_knn_scatter, dim3(ng), dim3(kBlock), 0, s, N, points, (const uint32_t *)w.cell_of, w.cursor, w.sorted);
+  return 0;
+}
+
+// the records of k_density_prep behind the index's workspace
+inline size_t density_rec_offset(uint32_t N, uint32_t K) { return align256(carve(nullptr, N, K).bytes); }
+
 }  // namespace gs_knn
 
 using namespace gs_knn;
@@ -522,29 +693,77 @@ int gsgen_knn(const float *points, uint32_t n_points, uint32_t K, float *dist2, 
   const uint32_t N = n_points;
   const Ws w = carve(workspace, N, K);
   if (w.bytes > workspace_bytes) return GSGEN_EWORKSPACE;
-  const uint32_t cap = cell_cap(N, K), M = cap + 3, T = (M + kScanTile - 1) / kScanTile;
-  const uint32_t nb = reduce_blocks(N), ng = (N + kBlock - 1) / kBlock;
+  const uint32_t cap = cell_cap(N, K);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_knn_bbox, dim3(nb), dim3(kBlock), 0, s, N, points, w.part);
-  hipLaunchKernelGGL(k_knn_bbox_final, dim3(1), dim3(64), 0, s, nb, (const float *)w.part, w.P);
-  for (int pass = 0; pass < 2; ++pass) {
-    if (int e = (int)hipMemsetAsync(w.hist, 0, sizeof(uint32_t) * 3 * kBins, s)) return e;
-    hipLaunchKernelGGL(k_knn_hist, dim3(nb), dim3(kBlock), 0, s, N, points, (const Params *)w.P, w.hist);
-    hipLaunchKernelGGL(k_knn_select, dim3(1), dim3(192), 0, s, (const uint32_t *)w.hist, w.P, cap, pass);
-  }
-  if (int e = (int)hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * (size_t)M, s)) return e;
-  hipLaunchKernelGGL(k_knn_count, dim3(ng), dim3(kBlock), 0, s, N, cap, points, (const Params *)w.P, w.cell_of, w.counts);
-  hipLaunchKernelGGL(k_knn_scan_tiles, dim3(T), dim3(kBlock), 0, s, M, (const uint32_t *)w.counts, w.tile_sum);
-  hipLaunchKernelGGL(k_knn_scan_sums, dim3(1), dim3(kBlock), 0, s, T, w.tile_sum);
-  hipLaunchKernelGGL(k_knn_scan_apply, dim3(T), dim3(kBlock), 0, s, M, (const uint32_t *)w.counts, (const uint32_t *)w.tile_sum,
-                     w.start, w.cursor);
-  hipLaunchKernelGGL(k_knn_scatter, dim3(ng), dim3(kBlock), 0, s, N, points, (const uint32_t *)w.cell_of, w.cursor, w.sorted);
+  if (int e = build_index(points, N, K, w, s)) return e;
   if (K <= 1) launch_query<1>(N, K, cap, w, dist2, idx, s);
   else if (K <= 2) launch_query<2>(N, K, cap, w, dist2, idx, s);
   else if (K <= 4) launch_query<4>(N, K, cap, w, dist2, idx, s);
   else if (K <= 8) launch_query<8>(N, K, cap, w, dist2, idx, s);
   else if (K <= 16) launch_query<16>(N, K, cap, w, dist2, idx, s);
   else launch_query<32>(N, K, cap, w, dist2, idx, s);
+  return (int)hipGetLastError();
+}
+
+size_t gsgen_knn_query_workspace_bytes(uint32_t n_points, uint32_t n_queries, uint32_t K) {
+  (void)n_queries;  // (the queries are read in place: the workspace is the index)
+  if (n_points == 0 || K == 0 || K > 32) return 0;
+  return carve(nullptr, n_points, K).bytes;
+}
+
+int gsgen_knn_query(const float *points, uint32_t n_points, const float *queries, uint32_t n_queries, uint32_t K, float *dist2,
+                    int32_t *idx, void *workspace, size_t workspace_bytes, gsgen_stream_t stream) {
+  if (K == 0 || K > 32) return GSGEN_EUNSUPPORTED;
+  if (n_points == 0 || K > n_points || n_points > 0x7fffffffu) return GSGEN_EINVAL;
+  if (n_queries == 0) return 0;
+  if (!points || !queries || !dist2 || !idx || !workspace) return GSGEN_EINVAL;
+  const uint32_t N = n_points, Q = n_queries;
+  const Ws w = carve(workspace, N, K);
+  if (w.bytes > workspace_bytes) return GSGEN_EWORKSPACE;
+  const uint32_t cap = cell_cap(N, K);
+  hipStream_t s = (hipStream_t)stream;
+  if (int e = build_index(points, N, K, w, s)) return e;
+  if (K <= 1) launch_query_ext<1>(Q, K, cap, w, queries, dist2, idx, s);
+  else if (K <= 2) launch_query_ext<2>(Q, K, cap, w, queries, dist2, idx, s);
+  else if (K <= 4) launch_query_ext<4>(Q, K, cap, w, queries, dist2, idx, s);
+  else if (K <= 8) launch_query_ext<8>(Q, K, cap, w, queries, dist2, idx, s);
+  else if (K <= 16) launch_query_ext<16>(Q, K, cap, w, queries, dist2, idx, s);
+  else launch_query_ext<32>(Q, K, cap, w, queries, dist2, idx, s);
+  return (int)hipGetLastError();
+}
+
+size_t gsgen_density_grid_workspace_bytes(uint32_t n_points, uint32_t K) {
+  // (the index of a K + 1 search has no more cells than that of a K search: this size serves skip_nearest 0 and 1)
+  if (n_points == 0 || K == 0 || K > 32) return 0;
+  return density_rec_offset(n_points, K) + align256(2 * sizeof(float4) * (size_t)n_points) + 256;
+}
+
+int gsgen_density_grid(const float *mean, const float *qvec, const float *scale, const float *opacity, uint32_t N, const float *axis_x,
+                       const float *axis_y, const float *axis_z, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t K,
+                       uint32_t skip_nearest, float *out, void *workspace, size_t workspace_bytes, gsgen_stream_t stream) {
+  if (skip_nearest > 1) return GSGEN_EINVAL;
+  const uint32_t Ks = K + skip_nearest;  // the list that is searched
+  if (K == 0 || K > 32 || Ks > 32) return GSGEN_EUNSUPPORTED;
+  if (N == 0 || Ks > N || N > 0x7fffffffu) return GSGEN_EINVAL;
+  if (nx == 0 || ny == 0 || nz == 0) return 0;
+  if (!mean || !qvec || !scale || !opacity || !axis_x || !axis_y || !axis_z || !out || !workspace) return GSGEN_EINVAL;
+  const unsigned long long bricks = (unsigned long long)((nx + 3) / 4) * ((ny + 3) / 4) * ((nz + 3) / 4);
+  if (bricks > 0x7fffffffull) return GSGEN_EINVAL;
+  if (gsgen_density_grid_workspace_bytes(N, K) > workspace_bytes) return GSGEN_EWORKSPACE;
+  const Ws w = carve(workspace, N, Ks);
+  // (behind the index of the K search's size, which is the larger: one layout for both values of skip_nearest)
+  float4 *rec = (float4 *)((char *)w.P + density_rec_offset(N, K));
+  const uint32_t cap = cell_cap(N, Ks);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_density_prep, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, qvec, scale, opacity, rec);
+  if (int e = build_index(mean, N, Ks, w, s)) return e;
+  const uint32_t blocks = (uint32_t)((bricks + kBlock / 64 - 1) / (kBlock / 64));
+  if (Ks <= 1) launch_density<1>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  else if (Ks <= 2) launch_density<2>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  else if (Ks <= 4) launch_density<4>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  else if (Ks <= 8) launch_density<8>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  else if (Ks <= 16) launch_density<16>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  else launch_density<32>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
   return (int)hipGetLastError();
 }
 

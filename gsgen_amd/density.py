@@ -1,0 +1,71 @@
+"""The Gaussian density lattice of the mesh export (utils/export.py:20-120) on the GPU: gsgen_density_grid (gsgen_amd/csrc/knn.hip).
+
+For every point of a reso^3 lattice over [-L, L]^3 the reference searches the K + 1 nearest Gaussian centres (pytorch3d, in batches
+of 256 lattice points), drops the nearest and sums opacity * exp(-1/2 d^T Sigma^-1 d) over the K others.  Here one fused launch does
+the search and the sum: no index or distance array is written.  Marching cubes (PyMCubes, host code) and the file writing of
+`to_mesh` are not part of this package: feed the returned grid to them.
+
+The functions take CUDA (HIP) tensors, run on the current stream without host synchronisation (get_density_val_grid_from_ckpt's
+`L < 0` takes the reference's own `.item()`), record no autograd graph, and can be captured by `torch.cuda.graph`.
+"""
+import torch
+
+from . import _capi
+from .knn import K_MAX
+
+
+def _lib():
+    lib = _capi.load()
+    if not hasattr(lib, "density_grid"):
+        raise RuntimeError(f"{lib.path} was built without gsgen_density_grid (gsgen_amd/csrc/knn.hip): rebuild it "
+                           "(python -m gsgen_amd.build)")
+    return lib
+
+
+@torch.no_grad()
+def density_grid_axes(mean, qvec, scale, opacity, axis_x, axis_y, axis_z, K=3, skip_nearest=True):
+    """the kernel's own form: lattice coordinates as three 1-D tensors -> [len(axis_x), len(axis_y), len(axis_z)] float32"""
+    K, skip = int(K), int(bool(skip_nearest))
+    if mean.dim() != 2 or mean.shape[1] != 3 or not mean.is_cuda:
+        raise ValueError(f"gsgen_amd.density: mean must be a [N, 3] CUDA (HIP) tensor, got {tuple(mean.shape)} on {mean.device}")
+    N, dev = mean.shape[0], mean.device
+    if not 1 <= K or K + skip > K_MAX:
+        raise ValueError(f"gsgen_amd.density: K + skip_nearest = {K + skip} is not in 1..{K_MAX}")
+    if N == 0 or K + skip > N:
+        raise ValueError(f"gsgen_amd.density: {K + skip} neighbours of {N} Gaussians")
+    if tuple(qvec.shape) != (N, 4) or tuple(scale.shape) != (N, 3) or opacity.numel() != N:
+        raise ValueError(f"gsgen_amd.density: qvec {tuple(qvec.shape)}, scale {tuple(scale.shape)}, opacity {tuple(opacity.shape)} "
+                         f"for {N} Gaussians")
+    f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    mean, qvec, scale, opacity = f(mean), f(qvec), f(scale), f(opacity).reshape(-1)
+    ax, ay, az = (f(a).reshape(-1) for a in (axis_x, axis_y, axis_z))
+    lib = _lib()
+    out = torch.empty(ax.numel(), ay.numel(), az.numel(), device=dev, dtype=torch.float32)
+    nbytes = lib.density_grid_workspace_bytes(N, K)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    lib.density_grid(mean.data_ptr(), qvec.data_ptr(), scale.data_ptr(), opacity.data_ptr(), N, ax.data_ptr(), ay.data_ptr(),
+                     az.data_ptr(), ax.numel(), ay.numel(), az.numel(), K, skip, out.data_ptr(), ws.data_ptr(), nbytes,
+                     torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+@torch.no_grad()
+def density_grid(mean, qvec, scale, opacity, L, reso, K=3, skip_nearest=True):
+    """-> [reso, reso, reso] float32 on the device: the density at the points of torch.linspace(-L, L, reso)^3 (indexing "ij": x
+    slowest), from activated scale [N,3] and opacity [N].  skip_nearest=True is the reference: the K + 1 nearest centres with the
+    nearest dropped (utils/export.py:94-96 through utils/ops.py:129-134); False sums the K nearest.  The lattice coordinates are
+    torch.linspace's on the device of `mean` (density_grid_axes takes coordinates of the caller's own)."""
+    axis = torch.linspace(-L, L, int(reso), device=mean.device)
+    return density_grid_axes(mean, qvec, scale, opacity, axis, axis, axis, K, skip_nearest)
+
+
+@torch.no_grad()
+def get_density_val_grid_from_ckpt(ckpt, batch_size=256, L=-1.0, reso=128, K=3):
+    """utils/export.py:66-120 -> (grid [reso,reso,reso], L): ckpt holds the raw fields "mean", "qvec", "svec" (log scale) and "alpha"
+    (logit opacity) on the GPU.  L < 0 takes mean.abs().max().item() * 1.1 -- one host sync, the reference's own.  batch_size is
+    accepted for the signature and ignored: the lattice is one launch."""
+    del batch_size
+    if L < 0.0:
+        L = ckpt["mean"].abs().max().item() * 1.1
+    grid = density_grid(ckpt["mean"], ckpt["qvec"], torch.exp(ckpt["svec"]), torch.sigmoid(ckpt["alpha"]), L, reso, K, True)
+    return grid, L

@@ -6,8 +6,11 @@ the current stream. The workspace comes from torch's caching allocator. They rec
 the host, so a call can be captured by `torch.cuda.graph` and replayed on new point values in the same tensor.  The exception is
 nearest_neighbor_initialize, which returns its result on the CPU as the reference does.
 
-Neighbour order: ascending squared distance, ties by ascending index.  Each point is its own first neighbour unless a lower-index
-exact duplicate of it exists.  A point with a NaN / Inf coordinate is nobody's neighbour; its row, and any row short of K finite
+With `query=None` every point is also a query (the self search); with a `[Q,3]` query tensor row q lists the neighbours of
+query[q] among `points` (gsgen_knn_query), d = p_j - q.
+
+Neighbour order: ascending squared distance, ties by ascending index.  In the self search each point is its own first neighbour
+unless a lower-index exact duplicate of it exists.  A non-finite query's row is all (-1, +inf).  A point with a NaN / Inf coordinate is nobody's neighbour; its row, and any row short of K finite
 points, holds index -1 and distance +inf.
 """
 import numpy as np
@@ -38,14 +41,36 @@ def _check_points(points, K):
     return N
 
 
+def _check_query(points, query):
+    if not isinstance(query, torch.Tensor) or query.dim() != 2 or query.shape[1] != 3:
+        raise ValueError(f"gsgen_amd.knn: query must be a [Q, 3] tensor, got {getattr(query, 'shape', type(query))}")
+    if not query.is_cuda:
+        raise NotImplementedError("gsgen_amd.knn: a query set on the CPU -- there is no CPU implementation of the query search")
+    if query.device != points.device:
+        raise ValueError("gsgen_amd.knn: query must be on the device of points")
+    return query.shape[0]
+
+
 @torch.no_grad()
-def knn_raw(points, K):
-    """-> (dist2 [N,K] float32, idx [N,K] int32): the kernel's own output"""
+def knn_raw(points, K, query=None):
+    """-> (dist2 [N,K] float32, idx [N,K] int32): the kernel's own output; with query [Q,3]: [Q,K], the neighbours of each query"""
     K = int(K)
+    Q = _check_query(points, query) if query is not None else None
     N = _check_points(points, K)
     pts = points.detach().to(torch.float32).contiguous()
     dev = pts.device
     lib = _lib()
+    if query is not None:
+        if not hasattr(lib, "knn_query"):
+            raise RuntimeError(f"{lib.path} was built without gsgen_knn_query: rebuild it (python -m gsgen_amd.build)")
+        qs = query.detach().to(torch.float32).contiguous()
+        dist2 = torch.empty(Q, K, device=dev, dtype=torch.float32)
+        idx = torch.empty(Q, K, device=dev, dtype=torch.int32)
+        nbytes = lib.knn_query_workspace_bytes(N, Q, K)
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        lib.knn_query(pts.data_ptr(), N, qs.data_ptr(), Q, K, dist2.data_ptr(), idx.data_ptr(), ws.data_ptr(), nbytes,
+                      torch.cuda.current_stream(dev).cuda_stream)
+        return dist2, idx
     dist2 = torch.empty(N, K, device=dev, dtype=torch.float32)
     idx = torch.empty(N, K, device=dev, dtype=torch.int32)
     nbytes = lib.knn_workspace_bytes(N, K)
@@ -56,10 +81,10 @@ def knn_raw(points, K):
 
 
 @torch.no_grad()
-def knn_points(points, K):
+def knn_points(points, K, query=None):
     """self kNN of points [N,3] -> (dist2 [N,K] float32, squared distances; idx [N,K] int64), pytorch3d's knn_points(p[None],
-    p[None], K) without the batch axis"""
-    dist2, idx = knn_raw(points, K)
+    p[None], K) without the batch axis; with query [Q,3]: knn_points(query[None], p[None], K), [Q,K]"""
+    dist2, idx = knn_raw(points, K, query)
     return dist2, idx.long()
 
 
@@ -73,10 +98,11 @@ def nearest_neighbor(mean):
 
 @torch.no_grad()
 def K_nearest_neighbors(mean, K, query=None, return_dist=False):
-    """utils/ops.py:117-134: a K search with column 0 (the point itself) dropped -> (nn [N,K-1,3], idx [N,K-1](, dist2 [N,K-1]))"""
-    if query is not None:
-        raise NotImplementedError("gsgen_amd.knn.K_nearest_neighbors: a query set other than the points themselves")
-    dist2, idx = knn_points(mean, K)
+    """utils/ops.py:117-134: a K search with column 0 (the point itself) dropped -> (nn [N,K-1,3], idx [N,K-1](, dist2 [N,K-1])).
+    With query [Q,3] the rows are the queries' ([Q,K-1,...]) and column 0 -- then the query's NEAREST point, not the query -- is
+    dropped all the same: that is the reference's behaviour (utils/ops.py:129-134 slices [1:] whatever the query set is, and its
+    density grid, utils/export.py:94-96, relies on it), not an oversight of this port."""
+    dist2, idx = knn_points(mean, K, query)
     idx = idx[:, 1:]
     nn = mean.detach()[idx]
     return (nn, idx, dist2[:, 1:]) if return_dist else (nn, idx)

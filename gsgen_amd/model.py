@@ -650,5 +650,15 @@ class GaussianSplattingRenderer(nn.Module):
         if hasattr(writer, "add_histogram"):
             writer.add_histogram("hists/max_radii2d", self.max_radii2d, step)
 
+    @torch.no_grad()
+    def get_density_val_grid(self, L=-1.0, reso=128, K=3):
+        """utils/export.py:20-63 / gs/gaussian_splatting.py:1567: the density lattice of the mesh export from the model's activated
+        fields (gsgen_amd.density: one fused search + sum launch) -> [reso,reso,reso] float32.  L < 0: mean.abs().max() * 1.1,
+        one host sync as in the reference."""
+        from .density import density_grid
+        if L < 0.0:
+            L = self.mean.abs().max().item() * 1.1
+        return density_grid(self.mean, self.qvec, self.svec, self.alpha, L, reso, K, True)
+
     def get_params_for_save(self):  # gs/gaussian_splatting.py:294-311 (the five raw fields; gsgen_amd.io writes them)
         return {k: getattr(self, k).detach() for k in self.raw_fields}

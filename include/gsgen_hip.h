@@ -726,7 +726,7 @@ int gsgen_vol_render_rgb_backward_batch(uint32_t n_views, const gsgen_rgbd_view 
                                         uint32_t n_tiles_w, uint32_t H, uint32_t W, float thresh,
                                         void *batch_workspace, gsgen_stream_t stream);
 
-/* ---- exact self k-nearest neighbours (gsgen_amd/csrc/knn.hip) --------------------------------------------------------
+/* ---- exact k-nearest neighbours (gsgen_amd/csrc/knn.hip) --------------------------------------------------------
  * replaces pytorch3d's knn_points as utils/ops.py:104-134 calls it (and faiss IndexFlatL2, utils/initialize.py:16-35).
  * points [n_points,3] fp32; every point is also a query.  Row i of dist2 [n_points,K] fp32 / idx [n_points,K] int32 lists the K
  * nearest points in ascending (dist2, index) order, dist2 = dx*dx + dy*dy + dz*dz with d = p_j - p_i evaluated left to right
@@ -739,6 +739,32 @@ int gsgen_vol_render_rgb_backward_batch(uint32_t n_views, const gsgen_rgbd_view 
 size_t gsgen_knn_workspace_bytes(uint32_t n_points, uint32_t K);
 int gsgen_knn(const float *points, uint32_t n_points, uint32_t K, float *dist2, int32_t *idx, void *workspace,
               size_t workspace_bytes, gsgen_stream_t stream);
+
+/* The same search for a query set of its own: queries [n_queries,3] fp32, taken in the caller's order.  Row q of dist2 / idx
+ * [n_queries,K] lists the K nearest `points` to queries[q] in ascending (dist2, index) order, dist2 = dx*dx + dy*dy + dz*dz with
+ * d = p_j - q evaluated left to right (an fp32 brute force reproduces every bit).  A non-finite point is nobody's neighbour; a
+ * non-finite query's row is (-1, +inf), and so is the tail of a row short of K finite points.  K in 1..32 (else
+ * GSGEN_EUNSUPPORTED); n_points == 0, K > n_points or a null pointer: GSGEN_EINVAL; n_queries == 0: 0 (success), nothing enqueued.
+ * The index over `points` is rebuilt by every call (the workspace holds it: gsgen_knn_query_workspace_bytes).  Launch shapes
+ * depend on (n_points, n_queries, K) alone; no host synchronisation, no allocation: capturable. */
+size_t gsgen_knn_query_workspace_bytes(uint32_t n_points, uint32_t n_queries, uint32_t K);
+int gsgen_knn_query(const float *points, uint32_t n_points, const float *queries, uint32_t n_queries, uint32_t K, float *dist2,
+                    int32_t *idx, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
+
+/* The density lattice of the mesh export (utils/export.py:66-120, get_density_val_grid_from_ckpt), fused with the search:
+ * out[(ix*ny + iy)*nz + iz] = sum over the kept neighbours j of opacity_j * exp(-0.5 * d^T Sigma_j^-1 d),
+ * d = (axis_x[ix], axis_y[iy], axis_z[iz]) - mean_j.  The neighbours are the K + skip_nearest nearest centres of the lattice
+ * point (order and ties as gsgen_knn_query) with the first skip_nearest (0 or 1) dropped -- the reference searches K + 1 and
+ * drops column 0, so 1 reproduces it.  A missing neighbour (fewer finite centres than asked for, a non-finite lattice
+ * coordinate) contributes 0.  Sigma_j^-1 = R diag(1 / scale^2) R^T in closed form from qvec [N,4] (w first, normalised as the
+ * projection does) and the ACTIVATED scale [N,3]; opacity [N] activated.  K + skip_nearest in 1..32 (else GSGEN_EUNSUPPORTED);
+ * N == 0, K + skip_nearest > N, skip_nearest > 1 or a null pointer: GSGEN_EINVAL; an empty lattice: 0 (success).
+ * workspace: gsgen_density_grid_workspace_bytes(N, K), for either value of skip_nearest.  Capturable like gsgen_knn. */
+size_t gsgen_density_grid_workspace_bytes(uint32_t n_points, uint32_t K);
+int gsgen_density_grid(const float *mean, const float *qvec, const float *scale, const float *opacity, uint32_t N,
+                       const float *axis_x, const float *axis_y, const float *axis_z, uint32_t nx, uint32_t ny, uint32_t nz,
+                       uint32_t K, uint32_t skip_nearest, float *out, void *workspace, size_t workspace_bytes,
+                       gsgen_stream_t stream);
 
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
