@@ -26,6 +26,7 @@ SOURCES = {
     "binning.hip": [],
     "legacy.hip": ["-ffp-contract=off"],
     "knn.hip": ["-ffp-contract=off"],  # dist2 bit-identical to an fp32 brute force (see the file header)
+    "fps.hip": ["-ffp-contract=off"],  # d2 bit-identical to an fp32 NumPy loop (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three
 # cross-file helpers used to be exported beside them)
@@ -36,8 +37,7 @@ def _newer(src, dst, extra=()):
     if not os.path.exists(dst):
         return True
     t = os.path.getmtime(dst)
-    deps = [src, os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "composite_common.hpp"),
-            
+    deps = [src, os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "composite_common.hpp"), os.path.join(CSRC, "knn_index.hpp"),
             os.path.join(HERE, "..", "include", "gsgen_hip.h"), __file__, *extra]
     return any(os.path.getmtime(d) > t for d in deps)
 

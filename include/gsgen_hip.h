@@ -42,7 +42,7 @@ extern "C" {
 
 typedef void *gsgen_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
-#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32 */
+#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method */
 #define GSGEN_EINVAL (-3)       /* null pointer / inconsistent sizes */
 #define GSGEN_EWORKSPACE (-4)   /* workspace too small */
 
@@ -765,6 +765,24 @@ int gsgen_density_grid(const float *mean, const float *qvec, const float *scale,
                        const float *axis_x, const float *axis_y, const float *axis_z, uint32_t nx, uint32_t ny, uint32_t nz,
                        uint32_t K, uint32_t skip_nearest, float *out, void *workspace, size_t workspace_bytes,
                        gsgen_stream_t stream);
+
+/* ---- exact farthest point sampling (gsgen_amd/csrc/fps.hip) ------------------------------------------------------
+ * replaces pytorch3d's sample_farthest_points as utils/ops.py:76-100 calls it (guidance/point_e.py:120-127, :169-179).
+ * points fp32, n_starts clouds of [n_points, dim] rows, cloud_stride floats between the clouds of consecutive starts (0: every
+ * start samples the same cloud).  lengths: device int32[n_starts] (cloud b is its first lengths[b] rows) or null; start_idx:
+ * device int32[n_starts], read by the kernel; idx_out: device int32[n_starts, K].
+ * Row b: idx[0] = start_idx[b] (the lowest-index finite point when that is out of range or not finite); m[p] = +inf; after pick s,
+ * m[p] = min(m[p], d2(p, s)), d2 = sum over the coordinates of (p_c - s_c)^2 left to right in fp32 (an fp32 loop reproduces every
+ * bit); the next pick is the point of the largest m, ties to the lowest index.  A point with a NaN / Inf coordinate is never
+ * picked; entries past the number of pickable points are -1.
+ * method: 0 auto, 1 brute (dim 3 or 6), 2 bucket-pruned (dim 3; same result).  Another dim, method or pair: GSGEN_EUNSUPPORTED
+ * (workspace size 0).  K == 0, n_points == 0, n_starts == 0, a null pointer or a workspace smaller than
+ * gsgen_fps_workspace_bytes of the same sizes and method: GSGEN_EINVAL.  Launch shapes depend on the sizes alone; no allocation, no
+ * host synchronisation: capturable, and a replay samples from the starts and point values then in the buffers. */
+size_t gsgen_fps_workspace_bytes(uint32_t n_points, uint32_t dim, uint32_t n_starts, uint32_t K, int method);
+int gsgen_fps(const float *points, uint32_t n_points, uint32_t dim, size_t cloud_stride, const int32_t *lengths,
+              const int32_t *start_idx, uint32_t n_starts, uint32_t K, int32_t *idx_out, void *workspace, size_t workspace_bytes,
+              int method, gsgen_stream_t stream);
 
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
