@@ -922,12 +922,52 @@ __device__ __forceinline__ bool routed_tile_is_polynomial(const CompParams &p, u
   if (p.sh_bound != nullptr && poly_route(p.sh_bound, p.psx, p.psy)) return true;
   return p.sh_rows != nullptr && tile_list_within_bound(p, bid);
 }
+// ---- pixel sizes from device memory (gsgen_sh_view::pixel_size_dev) --------------------------------------------------------------
+// The batched SH launches whose views carry the pointer run the <..., PSD = true> instantiations of k_composite_*_sh_vec: the same
+// three shapes (exact, polynomial, persistent exact fallback), the view's {psx, psy} taken from DEVICE memory -- two scalar loads per
+// workgroup, in front of every decision that depends on them (poly_route, the fallback's scan of the batch) -- and written into the
+// workgroup's own copy of the parameter block, from which the tile bodies take them as ever (pixel_coord, exact_tier_mask,
+// poly_tile_setup).  A captured hipGraph of such a launch replays for other intrinsics.  A COMPILE-time flag, so that the kernels
+// every launch without the pointer runs are what they were: no runtime test of the pointer in them (one was measured in round 6:
+// -0.25 .. -0.6 % on the headline, profiles/r06_notes.md section 21; the fold itself: profiles/r08_notes.md).
+// PixelSizes<false> is a view of the block's own two floats, read where they are used as before; PixelSizes<true> holds the loaded pair.
+template <bool PSD>
+struct PixelSizes {
+  const CompParams &v;
+  __device__ float x() const { return v.psx; }
+  __device__ float y() const { return v.psy; }
+};
+template <>
+struct PixelSizes<true> {
+  float px, py;
+  __device__ float x() const { return px; }
+  __device__ float y() const { return py; }
+};
+template <bool PSD>
+__device__ __forceinline__ PixelSizes<PSD> view_pixel_sizes(const CompParams &v) {
+  if constexpr (PSD) {
+    const uniform_floats q = uniform_pointer(v.ps_dev);
+    return PixelSizes<true>{q[0], q[1]};
+  } else {
+    return PixelSizes<false>{v};
+  }
+}
+template <bool PSD>
+__device__ __forceinline__ CompParams view_params(const CompParams &v, const PixelSizes<PSD> &ps) {
+  CompParams p = v;
+  if constexpr (PSD) {
+    p.psx = ps.x();
+    p.psy = ps.y();
+  }
+  return p;
+}
 // TRACK = false (the batched polynomial kernel of an unsegmented launch only): no stop list to keep -- with the per-entry exact
 // tier's calls in the entry loop, those four registers decide whether the loop fits 96 without reloading spilled values per entry
-template <int CB, int PPL, bool BATCH = false, int NB = 0, bool TRACK = true>
+template <int CB, int PPL, bool BATCH = false, int NB = 0, bool TRACK = true, bool PSD = false>
 __global__ void __launch_bounds__(256 / PPL)
 GS_WAVES_PER_EU((NB == kPolyNB && BATCH && PPL == 4 && !TRACK) ? 5 : 1)  // that kernel: five wavefronts per SIMD (<= 96 registers)
 k_composite_fwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
+  static_assert(!PSD || (BATCH && NB != kRouted), "pixel sizes from device memory: the batched launches' three shapes");
   const CompParams *plist = pack.table();  // (kernel-argument memory: scalar loads, no table in device memory)
   uint32_t bid = blockIdx.x;
   if constexpr (NB == kRouted) {
@@ -954,7 +994,10 @@ k_composite_fwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
     const bool per_tile = plist[0].sh_rows != nullptr;  // (one mode per launch)
     if (!per_tile) {
       bool any = false;
-      for (uint32_t v = 0; v < B; ++v) any |= !poly_route(plist[v].sh_bound, plist[v].psx, plist[v].psy);
+      for (uint32_t v = 0; v < B; ++v) {
+        const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(plist[v]);
+        any |= !poly_route(plist[v].sh_bound, ps.x(), ps.y());
+      }
       if (!any) return;  // every view of the batch took the polynomial form
     }
     const uint32_t per = total / B;  // camera-major
@@ -963,92 +1006,28 @@ k_composite_fwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
     for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
       while (b >= base + per) { base += per; ++view; }
       const CompParams *pp = &plist[view];
+      const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(*pp);
       // per-view routing: the views the polynomial kernel left; per-tile routing (this launch runs BEHIND the polynomial
       // kernel): the tiles it flagged
-      if (per_tile ? !tile_flagged(*pp, b - base) : poly_route(pp->sh_bound, pp->psx, pp->psy)) continue;
-      const CompParams p = *pp;
+      if (per_tile ? !tile_flagged(*pp, b - base) : poly_route(pp->sh_bound, ps.x(), ps.y())) continue;
+      const CompParams p = view_params<PSD>(*pp, ps);
       composite_fwd_sh_vec_tile<4, PPL, 0, true>(p, b - base, sm);
       __syncthreads();  // the LDS block is reused by the next tile
     }
   } else if constexpr (NB == kPolyNB && BATCH) {
     __shared__ FwdShVecShared<4, true> sm;
     const CompParams *pp = &plist[batch_view(p_arg, bid)];
-    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, pp->psx, pp->psy);
+    const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(*pp);
+    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x(), ps.y());
     if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
-    CompParams p = *pp;
+    CompParams p = view_params<PSD>(*pp, ps);
     if (view_ok) p.sh_rows = nullptr;  // the whole scene is within this view's bound: no per-entry tests (tile_flags stay 0)
     composite_fwd_sh_vec_tile<4, PPL, kPolyNB, false, TRACK>(p, bid, sm);
   } else {
-    const CompParams p = BATCH ? plist[batch_view(p_arg, bid)] : p_arg;  // see k_composite_fwd
+    const CompParams *pp = BATCH ? &plist[batch_view(p_arg, bid)] : &p_arg;  // see k_composite_fwd
+    const CompParams p = view_params<PSD>(*pp, view_pixel_sizes<PSD>(*pp));
     __shared__ FwdShVecShared<CB, (NB > 0)> sm;
     composite_fwd_sh_vec_tile<CB, PPL, NB>(p, bid, sm);
-  }
-}
-
-// ---- pixel sizes from device memory (gsgen_sh_view::pixel_size_dev) --------------------------------------------------------------
-// The batched SH launches whose views carry the pointer run THESE kernels instead of k_composite_*_sh_vec<..., BATCH = true>: the same
-// three shapes (exact, polynomial, persistent exact fallback), the view's {psx, psy} taken from DEVICE memory -- two scalar loads per
-// workgroup, in front of every decision that depends on them (poly_route, the fallback's scan of the batch) -- and written into the
-// workgroup's own copy of the parameter block, from which the tile bodies take them as ever (pixel_coord, exact_tier_mask,
-// poly_tile_setup).  A captured hipGraph of such a launch replays for other intrinsics.  Kernels of their own, so that the ones every
-// launch without the pointer runs are what they were: no runtime test of the pointer in them (one was measured in round 6:
-// -0.25 .. -0.6 % on the headline, profiles/r06_notes.md section 21).
-struct PixelSizes { float x, y; };
-__device__ __forceinline__ PixelSizes view_pixel_sizes(const CompParams &v) {
-  const uniform_floats q = uniform_pointer(v.ps_dev);
-  return PixelSizes{q[0], q[1]};
-}
-__device__ __forceinline__ CompParams view_params_psd(const CompParams &v, const PixelSizes &ps) {
-  CompParams p = v;
-  p.psx = ps.x;
-  p.psy = ps.y;
-  return p;
-}
-template <int CB, int PPL, bool BATCH, int NB = 0, bool TRACK = true>  // (the template parameters of k_composite_fwd_sh_vec)
-__global__ void __launch_bounds__(256 / PPL)
-GS_WAVES_PER_EU((NB == kPolyNB && PPL == 4 && !TRACK) ? 5 : 1)  // (as k_composite_fwd_sh_vec)
-k_composite_fwd_psd_sh_vec(CompParams p_arg, ViewPack<true> pack) {
-  static_assert(BATCH && (NB == 0 || NB == kFallback || NB == kPolyNB), "the batched launches' three shapes");
-  const CompParams *plist = pack.table();
-  uint32_t bid = blockIdx.x;
-  if constexpr (NB == kFallback) {
-    static_assert(CB == 4, "the persistent exact fallback of a bounded batch");
-    __shared__ FwdShVecShared<4, false> sm;
-    const uint32_t B = (uint32_t)p_arg.n_lo, total = p_arg.vgrid;
-    const bool per_tile = plist[0].sh_rows != nullptr;  // (one mode per launch)
-    if (!per_tile) {
-      bool any = false;
-      for (uint32_t v = 0; v < B; ++v) {
-        const PixelSizes ps = view_pixel_sizes(plist[v]);
-        any |= !poly_route(plist[v].sh_bound, ps.x, ps.y);
-      }
-      if (!any) return;  // every view of the batch took the polynomial form
-    }
-    const uint32_t per = total / B;  // camera-major
-    uint32_t base = 0, view = 0;
-    for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
-      while (b >= base + per) { base += per; ++view; }
-      const CompParams *pp = &plist[view];
-      const PixelSizes ps = view_pixel_sizes(*pp);
-      if (per_tile ? !tile_flagged(*pp, b - base) : poly_route(pp->sh_bound, ps.x, ps.y)) continue;
-      const CompParams p = view_params_psd(*pp, ps);
-      composite_fwd_sh_vec_tile<4, PPL, 0, true>(p, b - base, sm);
-      __syncthreads();  // the LDS block is reused by the next tile
-    }
-  } else if constexpr (NB == kPolyNB) {
-    __shared__ FwdShVecShared<4, true> sm;
-    const CompParams *pp = &plist[batch_view(p_arg, bid)];
-    const PixelSizes ps = view_pixel_sizes(*pp);
-    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x, ps.y);
-    if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
-    CompParams p = view_params_psd(*pp, ps);
-    if (view_ok) p.sh_rows = nullptr;  // the whole scene is within this view's bound: no per-entry tests (tile_flags stay 0)
-    composite_fwd_sh_vec_tile<4, PPL, kPolyNB, false, TRACK>(p, bid, sm);
-  } else {
-    const CompParams *pp = &plist[batch_view(p_arg, bid)];
-    const CompParams p = view_params_psd(*pp, view_pixel_sizes(*pp));
-    __shared__ FwdShVecShared<CB, false> sm;
-    composite_fwd_sh_vec_tile<CB, PPL, 0>(p, bid, sm);
   }
 }
 
@@ -1765,11 +1744,12 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
 }
 // (the persistent fallback runs at 152 registers, the exact kernel at 148: three wavefronts per SIMD.  It only renders views whose
 // coefficient bound fails while a batch mate's holds.)
-template <int CB, int PPL, bool BATCH = false, int NB = 0, bool MOM = false>
+template <int CB, int PPL, bool BATCH = false, int NB = 0, bool MOM = false, bool PSD = false>  // PSD: see view_pixel_sizes
 __global__ void __launch_bounds__(256 / PPL)
 GS_WAVES_PER_EU((NB == kPolyNB && BATCH) ? 4 : 1)  // the batched polynomial backward: four wavefronts per SIMD (<= 128 registers)
 k_composite_bwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
   static_assert(!MOM || (BATCH && NB != kRouted), "the moment form exists for the batched launches");
+  static_assert(!PSD || (BATCH && NB != kRouted), "pixel sizes from device memory: the batched launches' three shapes");
   const CompParams *plist = pack.table();  // (kernel-argument memory: scalar loads, no table in device memory)
   uint32_t bid = blockIdx.x, grid = gridDim.x;
   if constexpr (NB == kRouted) {
@@ -1794,14 +1774,18 @@ k_composite_bwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
       const CompParams p = *pp;
       composite_bwd_sh_vec_tile<4, 4, 0>(p, bid, grid, sm.exact);
     }
-  } else if constexpr (NB == kFallback) {  // see k_composite_fwd_sh_vec
+  } else if constexpr (NB == kFallback) {  // see k_composite_fwd_sh_vec (the same walk: shared as ONE function taking the tile body, it
+                                           // changed the code of all four fallback kernels -- profiles/r08_notes.md section 3)
     static_assert(CB == 4 && PPL == 4 && BATCH, "the persistent exact fallback of a bounded batch");
     __shared__ BwdShVecShared<4, 4, false> sm;
     const uint32_t B = (uint32_t)p_arg.n_lo, total = p_arg.vgrid;
     const bool per_tile = plist[0].sh_rows != nullptr;
     if (!per_tile) {
       bool any = false;
-      for (uint32_t v = 0; v < B; ++v) any |= !poly_route(plist[v].sh_bound, plist[v].psx, plist[v].psy);
+      for (uint32_t v = 0; v < B; ++v) {
+        const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(plist[v]);
+        any |= !poly_route(plist[v].sh_bound, ps.x(), ps.y());
+      }
       if (!any) return;
     }
     const uint32_t per = total / B;  // camera-major
@@ -1811,73 +1795,26 @@ k_composite_bwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
     for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
       while (b >= base + per) { base += per; ++view; }
       const CompParams *pp = &plist[view];
-      if (per_tile ? !tile_flagged(*pp, (b - base) % tiles_grid) : poly_route(pp->sh_bound, pp->psx, pp->psy)) continue;
-      const CompParams p = *pp;
+      const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(*pp);
+      if (per_tile ? !tile_flagged(*pp, (b - base) % tiles_grid) : poly_route(pp->sh_bound, ps.x(), ps.y())) continue;
+      const CompParams p = view_params<PSD>(*pp, ps);
       composite_bwd_sh_vec_tile<4, 4, 0, true, MOM>(p, b - base, per, sm);
       __syncthreads();
     }
   } else if constexpr (NB == kPolyNB && BATCH) {
     __shared__ BwdShVecShared<4, 4, true> sm;
     const CompParams *pp = &plist[batch_view(p_arg, bid, &grid)];
-    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, pp->psx, pp->psy);
+    const PixelSizes<PSD> ps = view_pixel_sizes<PSD>(*pp);
+    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x(), ps.y());
     if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
-    CompParams p = *pp;
+    CompParams p = view_params<PSD>(*pp, ps);
     if (view_ok) p.sh_rows = nullptr;  // (as the forward: the same device value, the same decision)
     composite_bwd_sh_vec_tile<4, 4, kPolyNB, false, MOM>(p, bid, grid, sm);
   } else {
-    const CompParams p = BATCH ? plist[batch_view(p_arg, bid, &grid)] : p_arg;  // see k_composite_fwd
+    const CompParams *pp = BATCH ? &plist[batch_view(p_arg, bid, &grid)] : &p_arg;  // see k_composite_fwd
+    const CompParams p = view_params<PSD>(*pp, view_pixel_sizes<PSD>(*pp));
     __shared__ BwdShVecShared<CB, PPL, (NB > 0)> sm;
     composite_bwd_sh_vec_tile<CB, PPL, NB, false, MOM>(p, bid, grid, sm);
-  }
-}
-
-// pixel sizes from device memory: see k_composite_fwd_psd_sh_vec
-template <int CB, int PPL, bool BATCH, int NB = 0, bool MOM = false>  // (the template parameters of k_composite_bwd_sh_vec)
-__global__ void __launch_bounds__(64)
-GS_WAVES_PER_EU(NB == kPolyNB ? 4 : 1)  // (as k_composite_bwd_sh_vec)
-k_composite_bwd_psd_sh_vec(CompParams p_arg, ViewPack<true> pack) {
-  static_assert(PPL == 4 && BATCH && (NB == 0 || NB == kFallback || NB == kPolyNB), "the batched launches' three shapes");
-  const CompParams *plist = pack.table();
-  uint32_t bid = blockIdx.x, grid = gridDim.x;
-  if constexpr (NB == kFallback) {
-    static_assert(CB == 4, "the persistent exact fallback of a bounded batch");
-    __shared__ BwdShVecShared<4, 4, false> sm;
-    const uint32_t B = (uint32_t)p_arg.n_lo, total = p_arg.vgrid;
-    const bool per_tile = plist[0].sh_rows != nullptr;
-    if (!per_tile) {
-      bool any = false;
-      for (uint32_t v = 0; v < B; ++v) {
-        const PixelSizes ps = view_pixel_sizes(plist[v]);
-        any |= !poly_route(plist[v].sh_bound, ps.x, ps.y);
-      }
-      if (!any) return;
-    }
-    const uint32_t per = total / B;  // camera-major
-    const uint32_t tiles_grid = per / (uint32_t)(plist[0].nseg > 1 ? plist[0].nseg : 1);
-    uint32_t base = 0, view = 0;
-    for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
-      while (b >= base + per) { base += per; ++view; }
-      const CompParams *pp = &plist[view];
-      const PixelSizes ps = view_pixel_sizes(*pp);
-      if (per_tile ? !tile_flagged(*pp, (b - base) % tiles_grid) : poly_route(pp->sh_bound, ps.x, ps.y)) continue;
-      const CompParams p = view_params_psd(*pp, ps);
-      composite_bwd_sh_vec_tile<4, 4, 0, true, MOM>(p, b - base, per, sm);
-      __syncthreads();
-    }
-  } else if constexpr (NB == kPolyNB) {
-    __shared__ BwdShVecShared<4, 4, true> sm;
-    const CompParams *pp = &plist[batch_view(p_arg, bid, &grid)];
-    const PixelSizes ps = view_pixel_sizes(*pp);
-    const bool view_ok = pp->sh_bound != nullptr && poly_route(pp->sh_bound, ps.x, ps.y);
-    if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
-    CompParams p = view_params_psd(*pp, ps);
-    if (view_ok) p.sh_rows = nullptr;  // (as the forward: the same device value, the same decision)
-    composite_bwd_sh_vec_tile<4, 4, kPolyNB, false, MOM>(p, bid, grid, sm);
-  } else {
-    const CompParams *pp = &plist[batch_view(p_arg, bid, &grid)];
-    const CompParams p = view_params_psd(*pp, view_pixel_sizes(*pp));
-    __shared__ BwdShVecShared<CB, 4, false> sm;
-    composite_bwd_sh_vec_tile<CB, 4, 0, false, MOM>(p, bid, grid, sm);
   }
 }
 
@@ -2431,11 +2368,6 @@ static int launch_bwd(const CompParams &p_, hipStream_t s) {
 // caller's stream 4 959 (it finds room while the previous stage of the chain drains); behind it 4 919; on a side stream forked
 // from and joined into the caller's stream with events -- meant to hide the wait behind the polynomial kernel -- 4 725 (a fourth
 // and fifth hardware queue in play changes the arbitration for the worse).  Hence: in front, same stream, no extra objects.
-template <class Side, class Main>
-static void launch_beside(hipStream_t s, Side &&side, Main &&main) {
-  side(s);
-  main(s);
-}
 
 // ---- batched cameras: parameters through the kernel arguments -----------------------------------
 static ViewPack<true> make_pack(const CompParams *host, uint32_t n) {
@@ -2453,14 +2385,7 @@ static void for_each_chunk(const CompParams *host, uint32_t B, F &&f) {
     f(a, make_pack(host + b0, n), n);
   }
 }
-// PSD: the views carry gsgen_sh_view::pixel_size_dev -- the same launches, the device-pixel-size kernels (k_composite_*_psd_sh_vec)
-using ShBatchKernel = void (*)(CompParams, ViewPack<true>);
-template <bool PSD>
-static void launch_psd(ShBatchKernel plain, ShBatchKernel psd, dim3 grid, unsigned threads, hipStream_t s, const CompParams &p,
-                       const ViewPack<true> &plist) {
-  const ShBatchKernel k = PSD ? psd : plain;
-  hipLaunchKernelGGL(k, grid, dim3(threads), 0, s, p, plist);
-}
+// PSD: the views carry gsgen_sh_view::pixel_size_dev -- the same launches, the kernels' device-pixel-size instantiations
 template <int CB, bool PSD>
 static void launch_fwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &plist, uint32_t B, uint32_t nblk, hipStream_t s, bool bounded) {
   const dim3 g(nblk * B);
@@ -2474,25 +2399,25 @@ static void launch_fwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &pl
       CompParams pf = p0;
       pf.vgrid = nblk * B;
       const uint32_t gf = pf.vgrid < 2560u ? pf.vgrid : 2560u;
+      const auto fallback = [&] { hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 2, true, kFallback, true, PSD>), dim3(gf), dim3(128), 0, s, pf, plist); };
+      const auto polynomial = [&] {  // (TRACK: only a segmented launch keeps the stop list)
+        if (p0.stop == nullptr) hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false, PSD>), g, dim3(64), 0, s, p0, plist);
+        else hipLaunchKernelGGL((k_composite_fwd_sh_vec<4, 4, true, kPolyNB, true, PSD>), g, dim3(64), 0, s, p0, plist);
+      };
       if (p0.sh_rows != nullptr) {  // per-tile routing: the polynomial kernel flags the tiles the fallback BEHIND it renders
-        if (p0.stop == nullptr) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB, false>, g, 64, s, p0, plist);
-        else launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB>, g, 64, s, p0, plist);
+        polynomial();
         // (no_fallback: the caller's earlier batches reported no crowded tile -- nothing is handed over, nothing is launched)
-        if (!p0.no_fallback) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 2, true, kFallback>, k_composite_fwd_psd_sh_vec<4, 2, true, kFallback>, dim3(gf), 128, s, pf, plist);
+        if (!p0.no_fallback) fallback();
         return;
       }
-      launch_beside(
-          s, [&](hipStream_t q) { launch_psd<PSD>(k_composite_fwd_sh_vec<4, 2, true, kFallback>, k_composite_fwd_psd_sh_vec<4, 2, true, kFallback>, dim3(gf), 128, q, pf, plist); },
-          [&](hipStream_t q) {
-            if (p0.stop == nullptr) launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB, false>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB, false>, g, 64, q, p0, plist);
-            else launch_psd<PSD>(k_composite_fwd_sh_vec<4, 4, true, kPolyNB>, k_composite_fwd_psd_sh_vec<4, 4, true, kPolyNB>, g, 64, q, p0, plist);
-          });
+      fallback();  // (in front: see "where it goes" above)
+      polynomial();
       return;
     }
   }
   // exact basis: packed, two wavefronts per tile (a lone 8-view launch is 4 % slower than at four but issues fewer vector
   // instructions, which is what counts with another batch's backward in flight: 3 010 vs 2 885 renders/s, round 2)
-  launch_psd<PSD>(k_composite_fwd_sh_vec<CB, 2, true>, k_composite_fwd_psd_sh_vec<CB, 2, true>, g, 128, s, p0, plist);
+  hipLaunchKernelGGL((k_composite_fwd_sh_vec<CB, 2, true, 0, true, PSD>), g, dim3(128), 0, s, p0, plist);
 }
 template <bool PSD>
 static int launch_fwd_sh_batch_p(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
@@ -2524,18 +2449,15 @@ static void launch_bwd_sh_batch_c(const CompParams &p0, const ViewPack<true> &pl
       // 12 one-wavefront workgroups per compute unit (3 per SIMD: the exact body's occupancy at 152 registers) -- with per-tile
       // routing this launch may carry a large share of the tiles (2 per SIMD until round 4, when it only ever took whole views)
       const uint32_t gf = pf.vgrid < 3072u ? pf.vgrid : 3072u;
-      launch_beside(
-          s, [&](hipStream_t q) {
-            if (p0.sh_rows != nullptr && p0.no_fallback) return;  // (as the forward: no tile was handed over)
-            launch_psd<PSD>(k_composite_bwd_sh_vec<4, 4, true, kFallback, MOM>, k_composite_bwd_psd_sh_vec<4, 4, true, kFallback, MOM>, dim3(gf), 64, q, pf, plist);
-          },
-          [&](hipStream_t q) { launch_psd<PSD>(k_composite_bwd_sh_vec<4, 4, true, kPolyNB, MOM>, k_composite_bwd_psd_sh_vec<4, 4, true, kPolyNB, MOM>, g, 64, q, p0, plist); });
+      if (!(p0.sh_rows != nullptr && p0.no_fallback))  // (as the forward: no tile was handed over)
+        hipLaunchKernelGGL((k_composite_bwd_sh_vec<4, 4, true, kFallback, MOM, PSD>), dim3(gf), dim3(64), 0, s, pf, plist);
+      hipLaunchKernelGGL((k_composite_bwd_sh_vec<4, 4, true, kPolyNB, MOM, PSD>), g, dim3(64), 0, s, p0, plist);
       return;
     }
   }
   // one wavefront per tile: the per-Gaussian gradient reduction costs the same per wavefront whatever the number of pixels behind
   // it (two wavefronts per tile: 2 838 vs 3 492 renders/s on the exact basis, profiles/r04_ab_shapes.txt)
-  launch_psd<PSD>(k_composite_bwd_sh_vec<CB, 4, true, 0, MOM>, k_composite_bwd_psd_sh_vec<CB, 4, true, 0, MOM>, g, 64, s, p0, plist);
+  hipLaunchKernelGGL((k_composite_bwd_sh_vec<CB, 4, true, 0, MOM, PSD>), g, dim3(64), 0, s, p0, plist);
 }
 template <bool MOM, bool PSD>
 static int launch_bwd_sh_batch_m(int C, const CompParams *host, uint32_t B, hipStream_t s, bool bounded) {
@@ -2785,7 +2707,7 @@ static int fill_view_params(uint32_t n_views, const gsgen_sh_view *views, const 
     p.start = v.start; p.end = v.end; p.ids = v.gaussian_ids; p.topleft = v.topleft; p.rot = v.c2w;
     p.ntw = (int)ntw; p.nth = (int)nth; p.H = (int)H; p.W = (int)W;
     p.psx = v.pixel_size_x; p.psy = v.pixel_size_y; p.thresh = thresh;
-    p.ps_dev = v.pixel_size_dev;  // (set: the launch runs the k_composite_*_psd_sh_vec kernels, which ignore the two floats)
+    p.ps_dev = v.pixel_size_dev;  // (set: the launch runs the kernels' <..., PSD = true> instantiations, which ignore the two floats)
     p.tile_order = v.tile_order;
     p.n_hi = 0x7fffffff;
     p.sh_bound = sh_bound;  // (both given: the view's bound first -- a scene within it skips the per-entry tests --, then the rows)

@@ -68,8 +68,9 @@ struct CompParams {
   // and "no exact fallback is launched behind this kernel: keep every tile, take the per-entry exact tier"
   uint32_t *route_report;
   int no_fallback;
-  // RGB / RGB + heads, batched launches (gsgen_rgbd_view::pixel_size_dev): the view's {psx, psy} in device memory -- read at the top of
-  // the kernel in place of the two floats above, so that a captured step replays for other intrinsics (view_params below)
+  // Batched launches (gsgen_rgbd_view::pixel_size_dev, gsgen_sh_view::pixel_size_dev): the view's {psx, psy} in device memory -- read at
+  // the top of the kernel in place of the two floats above, so that a captured step replays for other intrinsics (RGB / RGB + heads:
+  // view_params below, a run-time test; SH: the <..., PSD = true> instantiations of k_composite_*_sh_vec, composite.hip)
   const float *ps_dev;
 };
 // a batched channel-mode kernel's parameter block: the view's entry of the kernel-argument table, pixel sizes from device memory if given

@@ -1761,7 +1761,9 @@ def test_no_kernel_spills_and_hot_kernels_keep_their_occupancy(tmp_path):
     allowed = ("k_composite_bwd_chan_vecILi3E", "k_composite_fwd_chan_vecILi3ELb1EE")
     # ... and the batched kernels that carry the polynomial SH body: its per-entry exact tier calls exact_tier_logits (8 bytes of
     # the callee's); whatever else they spill stays outside the entry loop (checked on the disassembly below)
-    tier = ("sh_vecILi4ELi4ELb1ELi6E",)  # (the per-camera kernels decide per tile before they touch it: no tier in their bodies)
+    # (the per-camera kernels decide per tile before they touch it: no tier in their bodies; the pattern takes both values of the
+    # kernels' last template argument, PSD -- pixel sizes from the parameter block | from device memory)
+    tier = ("sh_vecILi4ELi4ELb1ELi6E",)
     for k, v in spilling.items():
         assert (any(a in k for a in allowed) and v <= 16) or (any(a in k for a in tier) and v <= 96), spilling
     # disassembly: the entry loop -- the smallest loop (backward branch) that holds the body's calls, one gauss_ref and one
@@ -1796,7 +1798,7 @@ def test_no_kernel_spills_and_hot_kernels_keep_their_occupancy(tmp_path):
             assert 600 <= hi - lo <= 4000, (m.group(1), hi - lo)   # (150 .. 1000 instructions: an entry body -- with both colour tiers, Taylor and exponential, since round 5)
             assert not any(lo <= x <= hi for x in scratch), (m.group(1), hex(lo), hex(hi))
             n_checked += 1
-    assert n_checked >= 3, n_checked
+    assert n_checked >= 8, n_checked  # forward with / without the stop list, backward in both gradient forms, each at PSD = false | true
 
     def find(n, *parts):
         hits = [v for k, v in kernels.items() if all(p in k for p in parts)]
@@ -1806,28 +1808,29 @@ def test_no_kernel_spills_and_hot_kernels_keep_their_occupancy(tmp_path):
     # per-pixel arithmetic, channel-wise gradient reduction, grad_out in LDS, record in scalar registers): THREE wavefronts per
     # SIMD (<= 168 registers) and at least 12 workgroups per CU by LDS; per-camera and batched instantiation.
     # (round 6: the batched backward kernels exist in two forms -- <..., MOM = false> the plain gradients of the `_batch*` entry points,
-    # <..., MOM = true> the moment form BatchRenderer runs: the same budgets)
-    for bwd in find(1, "k_composite_bwd_sh_vecILi4ELi4ELb0ELi0ELb0EE") + find(2, "k_composite_bwd_sh_vecILi4ELi4ELb1ELi0ELb"):
+    # <..., MOM = true> the moment form BatchRenderer runs: the same budgets; and every batched SH kernel in two more -- <..., PSD = false>
+    # the pixel sizes of the parameter block, <..., PSD = true> the pair a captured step keeps in device memory: the same budgets)
+    for bwd in find(1, "k_composite_bwd_sh_vecILi4ELi4ELb0ELi0ELb0ELb0EE") + find(4, "k_composite_bwd_sh_vecILi4ELi4ELb1ELi0ELb"):
         assert bwd["vgpr_count"] <= 168 and 12 * bwd["group_segment_fixed_size"] <= 160 * 1024, bwd
     # SH degree 3 with the device-resident coefficient bound.  One camera: the ROUTED kernel (polynomial and exact form in one
     # launch, one LDS block shared by the two): the occupancy class of the exact kernel.  Camera batches: the polynomial form
     # alone -- FOUR wavefronts per SIMD in the backward, five in the one-wavefront-per-tile forward -- plus the persistent exact
     # fallback (the exact kernels' budgets).
-    for bwd in find(1, "k_composite_bwd_sh_vecILi4ELi4ELb0ELin1ELb0EE"):
+    for bwd in find(1, "k_composite_bwd_sh_vecILi4ELi4ELb0ELin1ELb0ELb0EE"):
         assert bwd["vgpr_count"] <= 168 and 12 * bwd["group_segment_fixed_size"] <= 160 * 1024, bwd
     for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi2ELb0ELin1E"):
         assert fwd["vgpr_count"] <= 96 and 10 * fwd["group_segment_fixed_size"] <= 160 * 1024, fwd
-    for bwd in find(2, "k_composite_bwd_sh_vecILi4ELi4ELb1ELi6ELb"):
+    for bwd in find(4, "k_composite_bwd_sh_vecILi4ELi4ELb1ELi6ELb"):
         assert bwd["vgpr_count"] <= 128 and 16 * bwd["group_segment_fixed_size"] <= 160 * 1024, bwd
     # (the forward of an unsegmented batch keeps no stop list: <..., TRACK = false>, the one held at five; a segmented batch's four)
-    for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb0EE"):
+    for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb0ELb0EE") + find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb0ELb1EE"):
         assert fwd["vgpr_count"] <= 96 and 20 * fwd["group_segment_fixed_size"] <= 160 * 1024, fwd
-    for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb1EE"):
+    for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb1ELb0EE") + find(1, "k_composite_fwd_sh_vecILi4ELi4ELb1ELi6ELb1ELb1EE"):
         assert fwd["vgpr_count"] <= 128 and 16 * fwd["group_segment_fixed_size"] <= 160 * 1024, fwd
     # (the persistent fallback: three wavefronts per SIMD in the backward as the exact kernel itself, four in the forward)
-    for bwd in find(2, "k_composite_bwd_sh_vecILi4ELi4ELb1ELin2ELb"):
+    for bwd in find(4, "k_composite_bwd_sh_vecILi4ELi4ELb1ELin2ELb"):
         assert bwd["vgpr_count"] <= 168 and 12 * bwd["group_segment_fixed_size"] <= 160 * 1024, bwd
-    for fwd in find(1, "k_composite_fwd_sh_vecILi4ELi2ELb1ELin2E"):
+    for fwd in find(2, "k_composite_fwd_sh_vecILi4ELi2ELb1ELin2E"):
         assert fwd["vgpr_count"] <= 128 and 8 * fwd["group_segment_fixed_size"] <= 160 * 1024, fwd
     # the trainer's default outputs (RGB + heads, packed, one wavefront per tile): FIVE wavefronts per SIMD backward, SIX forward
     for bwd in find(3, "k_composite_bwd_chan_vecILi3E"):  # per camera, batched, batched in the moment form
