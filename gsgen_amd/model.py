@@ -21,8 +21,8 @@ drop-in (gsgen_amd.install_as_gs) stays available for code that calls the 23 nam
 (bench.py reports both: `dropin_gs_surface` against `model_surface`).
 
 What is NOT carried over (raises NotImplementedError when configured or called): normal_as_rgb, pbr / specular shading, MLPBackground
-(tinycudann), overrides, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of update().  Penalty losses and
-compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
+(tinycudann), overrides of anything but `color`, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of
+update().  Penalty losses and compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
 The densify / prune policies themselves live in gsgen_amd.densify (this class delegates; AdaptiveControl is the multi-rank form on a
 FusedAdam), the flat-buffer optimiser in gsgen_amd.optim.
 """
@@ -321,6 +321,10 @@ class GaussianSplattingRenderer(nn.Module):
         near_plane, far_plane: the reference's utils/camera.py:219-259 or gsgen_amd.renderer.CameraInfo)}.
         -> {"rgb": [B,H,W,3]} + {"depth", "opacity", "z_var": [B,H,W,1]} unless rgb_only (gs/gaussian_splatting.py:1423-1466).
         use_bg is accepted and ignored, as in the reference (:1324-1327: the background is always composited)."""
+        return self._render(batch, use_bg, rgb_only)
+
+    def _render(self, batch, use_bg=True, rgb_only=False, color=None):
+        """forward's render; color: [N,3] activated colours in place of the model's (render_one's overrides)"""
         c2ws = batch["c2w"]
         if isinstance(c2ws, torch.Tensor):
             c2ws = c2ws.detach().to("cpu", torch.float32).numpy()  # (poses come from the data loader on the host: no sync there)
@@ -340,26 +344,35 @@ class GaussianSplattingRenderer(nn.Module):
         self.bg.static = self.device_cameras
         bg = self.bg(B, self.mean.device)
         fr = 0.0 if self.skip_frustum_culling else self.frustum_culling_radius
+        if color is not None and (not isinstance(color, torch.Tensor) or tuple(color.shape) != (self.N, 3)):
+            raise ValueError(f"gsgen_amd.model: a colour override must be a [{self.N}, 3] tensor, got {getattr(color, 'shape', type(color))}")
         if rgb_only:
-            rgb, _ = br.render(self.mean, self.qvec, self.svec, self.alpha, self.color, cis, c2ws, C=0, bg_rgb=bg, thresh=self.T_thresh,
+            rgb, _ = br.render(self.mean, self.qvec, self.svec, self.alpha, self.color if color is None else color, cis, c2ws, C=0,
+                               bg_rgb=bg, thresh=self.T_thresh,
                                frustum_radius=fr, tile_radius=self.tile_culling_radius, detach_depth=self.depth_detach, stats=stats)
             return {"rgb": rgb}
         # (z_var = depth2 - depth^2, :1397, the background, gs/renderer.py:1182, and the three activations, :113-124, are formed inside
         # the launches / the batch's autograd node: round 6)
+        # (an override is already activated: it goes through the launch's activation "nothing")
+        acts = self._act_names if color is None else (self._act_names[0], self._act_names[1], "nothing")
         rgb, depth, opacity, z_var, _ = br.render_heads(self.mean, self.qvec, self.svec_before_activation, self.alpha_before_activation,
-                                                        self.color_before_activation, cis, c2ws, bg_rgb=bg,
+                                                        self.color_before_activation if color is None else color, cis, c2ws, bg_rgb=bg,
                                                         thresh=self.T_thresh, frustum_radius=fr, tile_radius=self.tile_culling_radius,
                                                         detach_depth=self.depth_detach, stats=stats, z_var=True,
-                                                        activations=self._act_names)
+                                                        activations=acts)
         return {"rgb": rgb, "depth": depth, "opacity": opacity, "z_var": z_var}
 
     def render_one(self, c2w, camera_info, use_bg=True, rgb_only=False, overrides=None, return_T=False):
         """gs/gaussian_splatting.py:1198-1421 for one camera (the viewer's and the evaluation loop's call): -> the same dict
-        without the batch axis"""
-        if overrides:
-            raise NotImplementedError("gsgen_amd.model: overrides")
+        without the batch axis.  overrides: {"color": [N,3] activated colours} rendered in place of the model's (gradients flow to the
+        tensor), gs/gaussian_splatting.py:1178-1183, :1224-1228."""
+        color = None
+        for k in (overrides or {}):
+            if k != "color":
+                raise NotImplementedError(f"gsgen_amd.model: overrides[{k!r}] (only the colour can be overridden)")
+            color = overrides[k]
         c2w_np = c2w.detach().to("cpu", torch.float32).numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w, np.float32)
-        out = self.forward({"c2w": c2w_np[None], "camera_info": [camera_info]}, use_bg, rgb_only)
+        out = self._render({"c2w": c2w_np[None], "camera_info": [camera_info]}, use_bg, rgb_only, color=color)
         return {k: v[0] for k, v in out.items()}
 
     def post_backward(self):
