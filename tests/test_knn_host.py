@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from knn_cases import brute, clouds
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GSGEN_EUNSUPPORTED, GSGEN_EINVAL = -2, -3
 
@@ -35,53 +37,6 @@ def run_knn(lib, pts, K):
     rc = lib.gsgen_knn(pts.ctypes.data, N, K, d.ctypes.data, i.ctypes.data, ws.ctypes.data, ws.size, None)
     assert rc == 0, rc
     return d, i
-
-
-def brute(pts, K):
-    """fp32, d = p_j - p_i, dx*dx + dy*dy + dz*dz left to right; order (dist2, j); non-finite points are nobody's neighbour"""
-    pts = np.asarray(pts, np.float32)
-    N = pts.shape[0]
-    fin = np.isfinite(pts).all(1)
-    d = np.full((N, K), np.inf, np.float32)
-    idx = np.full((N, K), -1, np.int32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        dx = pts[None, :, 0] - pts[:, None, 0]
-        dy = pts[None, :, 1] - pts[:, None, 1]
-        dz = pts[None, :, 2] - pts[:, None, 2]
-        d2 = (dx * dx + dy * dy) + dz * dz
-    key = (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.arange(N, dtype=np.uint64)[None, :]
-    key[:, ~fin] = np.iinfo(np.uint64).max
-    for r in np.nonzero(fin)[0]:
-        k = np.sort(key[r])[:K]
-        ok = k != np.iinfo(np.uint64).max
-        n = int(ok.sum())
-        idx[r, :n] = (k[:n] & np.uint64(0xFFFFFFFF)).astype(np.int32)
-        d[r, :n] = (k[:n] >> np.uint64(32)).astype(np.uint32).view(np.float32)
-    return d, idx
-
-
-def clouds():
-    rng = np.random.default_rng(11)
-    out = {}
-    out["uniform"] = rng.uniform(-1, 1, (1500, 3))
-    centres = rng.normal(size=(12, 3))
-    out["clustered"] = centres[rng.integers(0, 12, 1800)] + 0.01 * rng.normal(size=(1800, 3))
-    base = rng.uniform(-1, 1, (600, 3))
-    dup = np.concatenate([base, base[rng.integers(0, 600, 400)], base[:50]])  # exact duplicates, some three times
-    out["duplicates"] = dup[rng.permutation(dup.shape[0])]
-    flat = rng.uniform(-1, 1, (1500, 3))
-    flat[:, 2] = 0.25
-    out["planar"] = flat
-    core = rng.normal(size=(1800, 3)) * 0.5
-    far = rng.normal(size=(40, 3))
-    out["outliers"] = np.concatenate([core, 100.0 * far / np.linalg.norm(far, axis=1, keepdims=True)])
-    nanc = rng.uniform(-1, 1, (1200, 3))
-    nanc[rng.integers(0, 1200, 30), rng.integers(0, 3, 30)] = np.nan
-    nanc[5, 1] = np.inf
-    nanc[17] = -np.inf
-    out["nan_rows"] = nanc
-    out["offset"] = rng.uniform(-1, 1, (800, 3)) * 1e-3 + np.array([1000.0, -2000.0, 500.0])  # far from the origin, fine spacing
-    return {k: v.astype(np.float32) for k, v in out.items()}
 
 
 CLOUDS = clouds()
