@@ -18,6 +18,14 @@
  * Layouts (row-major, fp32 unless noted): mean2d [N,2]; cov2d [N,2,2]; color [N,3];
  * alpha [N]; scalar [N]; sh_coeffs [N,3,C*C]; start/end int32 [n_tiles_h*n_tiles_w];
  * gaussian_ids int32 [D]; out [H,W,3] (or [H,W] scalar); T [H,W]; topleft [2]; bg_rgb [3].
+ * Alignment of the PARAMETER arrays (mean [N,3], qvec [N,4], svec [N,3], alpha, color, sh_coeffs and their gradients): 4 bytes, the
+ * type's own -- they may be views at any float offset into one larger buffer (gsgen_amd.optim.FusedAdam: qvec starts 3 N floats in,
+ * svec 7 N, sh_coeffs 11 N, so after a densify they are 16-byte aligned only where N % 4 == 0).  The projection reads mean / qvec /
+ * svec element by element; the SH kernels read a row of sh_coeffs (the staging of the exact kernels at C = 2 and 4, the polynomial
+ * transform at C = 4) as 16-byte loads from GLOBAL memory, which gfx950 performs at any dword address -- results do not depend on the
+ * base's alignment (tests/test_gpu_step_kernels.py renders bit-identical images from both).  The bound passes (gsgen_sh_l1_bound*)
+ * take their float4 kernels for a 16-byte aligned base at C = 4 and the row-per-thread kernels otherwise: the same bound within the
+ * rounding of the sum's order.  Arrays for which an entry point states 8 or 16 bytes below keep that requirement.
  * tile_size: 16 is the reference's only configured value (conf/base.yaml:132) and the size every tuned kernel variant,
  * the batched, segmented and fused entry points are built for.  The per-camera entry points of the `_gs` surface
  * (gsgen_tile_culling_aabb_count, gsgen_vol_render_start_end_with_T / _backward_start_end, _scalar / _scalar_backward,
@@ -253,6 +261,7 @@ int gsgen_adam_step_device_scalars(uint64_t n, float *param, const float *grad, 
  * aligned with mask [N] (NULL = all rows):
  *   max_radii2d[i] = max(max_radii2d[i], m + sqrt(max(m^2 - det(cov2d_i), 0))), m = tr/2
  *   grad_accum[i] += |grad_mean2d_i|_2 ;  cnt[i] += 1
+ * A NaN radius (NaN trace) sticks in max_radii2d, as torch.max does, also through later calls; a negative one never raises it.
  * Either pair (cov2d, max_radii2d) / (grad_mean2d, grad_accum[, cnt]) may be NULL together.
  * torch.det's LU rounding is not reproduced: det = c00*c11 - c01*c10 in fp32. */
 int gsgen_densify_update(uint32_t N, const float *cov2d, const float *grad_mean2d,

@@ -288,7 +288,7 @@ void gso_densify_update(int N, const float *cov2d, const float *g_mean2d, const 
       float mm = m * m;
       float d = mm - det;
       float r = m + sqrtf(d > 0.0f ? d : 0.0f);
-      if (r > max_radii2d[n]) max_radii2d[n] = r;
+      if (r > max_radii2d[n] || r != r) max_radii2d[n] = r; /* torch.max: a NaN radius sticks */
     }
     if (grad_accum) {
       float gx = g_mean2d[2 * n], gy = g_mean2d[2 * n + 1];
