@@ -163,7 +163,7 @@ OPTIONAL_SIZE_FUNCS = {
     "gsgen_fps_workspace_bytes": [u32, u32, u32, u32, i32],
 }
 EXPORTS = sorted(list(SIGNATURES) + list(SIZE_FUNCS) + list(PTR_FUNCS) + list(OPTIONAL_SIGNATURES) + list(OPTIONAL_SIZE_FUNCS)
-                 + ["gsgen_version", "gsgen_error_string", "gsgen_kernel_variant", "gsgen_sh_poly_applies"])
+                 + ["gsgen_version", "gsgen_error_string", "gsgen_kernel_variant", "gsgen_sh_poly_applies", "gsgen_emit_stage_capacity"])
 
 
 class GsgenError(RuntimeError):
@@ -231,6 +231,12 @@ class Lib:
 
     def version(self):
         return self.cdll.gsgen_version().decode()
+
+    def emit_stage_capacity(self):
+        """keys of one 2 048-Gaussian chunk that the push binning's emit pass groups by tile in LDS (a constant of the build)"""
+        fn = self.cdll.gsgen_emit_stage_capacity
+        fn.restype, fn.argtypes = u32, []
+        return int(fn())
 
     def sh_poly_applies(self, sh_l1_bound, max_pixel_size, bands=4):
         """the device's routing rule, on the host (for reports): does a view of this pixel size take the polynomial form of

@@ -23,11 +23,19 @@
 // so sort traffic is one read + one write of the pairs instead of 8 global radix passes, and
 // the result is deterministic: keys are unique.  Ordering semantics are the reference's: ascending UNSIGNED float bits of depth
 // (the low word of its int64 key), so negative depths sort after positive ones.
+// A camera batch (and a lone camera of 128 chunks or more) bins by PUSH instead (bin_push_body, below the sort): a workgroup per
+// chunk walks its Gaussians' rectangles with the per-tile counters in LDS; its emit pass groups the chunk's keys by tile in LDS
+// and stores them in runs, neighbouring lanes to neighbouring keys.  Same cnt / tile_count / tile_off, same scans, same sort.
 // Everything is enqueued on the caller's stream with no host synchronisation.
 #include "common.hpp"
 #include "../../include/gsgen_hip.h"
 #include <cstdlib>
 #include <vector>
+
+#if defined(GSGEN_EMU_KNOBS)
+extern "C" unsigned long long gsgen_emu_emit_staged_keys;
+unsigned long long gsgen_emu_emit_staged_keys = 0;
+#endif
 
 namespace gs {
 
@@ -645,8 +653,9 @@ k_scan_order_tiles_views(uint32_t T, const GeoView *__restrict__ views) {
 // 8 cfg2 views for 6 M (Gaussian, tile) pairs: a fifth of the RGB + heads step's.  Here a workgroup takes one chunk of ONE view,
 // every thread walks the rectangles of its Gaussians, and the per-tile counters live in LDS (T words: LDS atomics, a few dozen
 // per counter and chunk): COUNT leaves cnt[chunk][tile] exactly as the pull kernel does (same numbers, same layout, the same
-// k_scan_chunks behind it), EMIT starts each counter at the tile's segment offset + the chunk's prefix and takes slots from
-// it.  The slots of one chunk inside a segment come out in no particular order -- the sort behind it orders by (depth, id),
+// k_scan_chunks behind it), EMIT takes a key's slot inside its tile's run from the counter again (until round 7 the counter
+// started at the tile's segment offset + the chunk's prefix and the key was stored where its slot was; now only the tiles
+// beyond the staging array do that: "EMIT stages ..." below).  The slots of one chunk inside a segment come out in no particular order -- the sort behind it orders by (depth, id),
 // keys are unique, so the lists are the same bits as ever.  A rectangle of more than kPushOwn tiles is finished by the whole
 // wavefront (ballot, broadcast, 64 tiles at a time): one near Gaussian does not make 63 lanes wait for its 200 tiles.
 // (Counters in GLOBAL memory -- one atomic per pair on tile_count, no chunks -- were measured first: 3 620 instead of 5 440
@@ -654,7 +663,7 @@ k_scan_order_tiles_views(uint32_t T, const GeoView *__restrict__ views) {
 // the pull kernels.
 constexpr int kPushOwn = 12;
 constexpr uint32_t kPushMaxTiles = 8192;  // 32 KB of LDS: 2 048 x 1 024 pixels and the like
-constexpr int kPushThreads = 512;  // (round 6: 256 -> 512: the count launch 25 -> 18 us, the emit 72 -> 66 us per 8 cfg2 views alone; 1 024: 17 / 64, no better in flight: profiles/r06_s22_*)
+constexpr int kPushThreads = 512;  // (round 6: 256 -> 512: the count launch 25 -> 18 us, the emit 72 -> 66 us per 8 cfg2 views alone; 1 024: 17 / 64, no better in flight: profiles/r06_s22_*.  Round 7, with the staged emit: 256 threads 25 / 70 us alone against 18 / 47, -2.4 % with one step in flight: profiles/r07_notes.md section 6)
 constexpr uint32_t kPushMinWorkgroups = 128;  // (chunks x views) below which the pull kernels are the faster launch
 // A camera batch is a throughput launch (other steps' kernels fill the chip around it): there the fewer instructions win from
 // a quarter of that on.
@@ -667,29 +676,108 @@ static uint32_t push_min_workgroups(bool batch) {
   return batch ? kPushMinWorkgroupsBatch : kPushMinWorkgroups;
 }
 // the counters: T words of dynamic LDS (10 KB at 800 x 800: a workgroup finds room beside the compositing kernels' blocks
-// sooner than with the 32 KB of the largest image); the CPU emulator build has no dynamic LDS and takes the maximum
+// sooner than with the 32 KB of the largest image); the emit pass has its staging words behind them (below).  The CPU emulator
+// build has no dynamic LDS and takes the maximum of both
+#if !defined(GSGEN_EMIT_STAGE_WORDS)
+#define GSGEN_EMIT_STAGE_WORDS 12288  // (8 192 and 12 288 measured: the emit alone 44 / 47 us per 8 cfg2 views, in flight +2.1 / +2.9 % on the SH line: profiles/r07_notes.md)
+#endif
+// EMIT stages a chunk's keys in LDS, grouped by tile, and stores them in runs (round 7).  One scattered 8-byte store per key --
+// every lane of a store instruction in another 128-byte line, a tile's segment receiving ~6 keys per chunk -- wrote 152 MB for
+// 45.6 MB of keys per 8 cfg2 views and left the wavefronts 61 % of their cycles in s_waitcnt (profiles/r06_traffic.json).  Now:
+//   layout  this chunk's count of tile t is c_t = cnt[chunk + 1][t] - cnt[chunk][t] (tile_count[t] behind the last chunk: cnt is
+//           the exclusive prefix over chunks by now); a workgroup-wide exclusive scan of c_t over the tiles gives local_off[t],
+//           the chunk's own layout: tile after tile, each tile's keys together
+//   stage   visit() takes its slot from the tile's LDS cursor as before (it starts at local_off[t]) and writes ONE 32-bit word,
+//           (tile << 11) | (id - chunk base), into the staging array there -- both walks do
+//   flush   thread j takes staged word j, rebuilds the key (depth[id] is read again: 8 KB per chunk, cache hits; the chunk's depths
+//           kept in 8 KB of LDS instead measured 45 against 47 us alone and the same in flight: not worth the LDS) and stores it at
+//           j + gdelta[tile], gdelta[t] = tile_off[t] + cnt[chunk][t] - local_off[t]: neighbouring lanes write neighbouring
+//           keys of a run.  (gdelta takes the cursors' place once the walks are done: cursor[t - 1] has ended on local_off[t].)
+// The staging array holds kEmitStageWords keys (fewer on the largest images: counters and staging words together stay within
+// the 64 KB of LDS a launch gets without asking; emit_stage_cap).  Of a chunk with more, the leading tiles -- as many as fit: those with
+// local_off[t + 1] <= the capacity, a prefix of the tile range since local_off only grows -- are staged whole, and the keys
+// of the tiles behind them take the direct store at tile_off[t] + cnt[chunk][t] + slot as before (their cursors start there).
+// Splitting by TILE keeps every staged run at its full length; rounds over sub-ranges of the chunk's Gaussians would need the
+// tile counts of each sub-range (a second walk per round) and cut a run of six keys into rounds of two.  Any scene comes out
+// right: 2 048 Gaussians that cover every tile stage six tiles and store the rest directly.
+constexpr uint32_t kEmitStageWords = GSGEN_EMIT_STAGE_WORDS;
+constexpr int kEmitIdBits = 11;  // the id inside the chunk; the tile above it
+static_assert(kChunk == (1 << kEmitIdBits) && kPushMaxTiles <= (1u << (32 - kEmitIdBits)), "a staged word is (tile << 11) | local id");
+static_assert(kPushMaxTiles % kPushThreads == 0 && kPushThreads % 64 == 0, "bin_push_body");
 #if defined(__HIP_DEVICE_COMPILE__)
 #define GS_PUSH_COUNTERS(name) extern __shared__ uint32_t name[]
 #else
-#define GS_PUSH_COUNTERS(name) __shared__ uint32_t name[kPushMaxTiles]
+#define GS_PUSH_COUNTERS(name) __shared__ uint32_t name[kPushMaxTiles + kEmitAuxWords + kEmitStageWords]
 #endif
+constexpr uint32_t kEmitLdsWords = 16384;  // counters + scan words + staging words of an emit workgroup: 64 KB
+constexpr uint32_t kEmitAuxWords = 16;     // the scan's per-wavefront sums [kPushThreads / 64], then [14] staged tiles, [15] staged keys
+static_assert(kPushThreads / 64 <= 14 && kPushMaxTiles + kEmitAuxWords + 64 <= kEmitLdsWords && kEmitStageWords >= 64, "bin_push_body");
+__host__ __device__ __forceinline__ uint32_t emit_stage_cap(uint32_t T) { return min(kEmitStageWords, kEmitLdsWords - kEmitAuxWords - T); }
+static size_t push_lds_bytes(uint32_t T, bool emit) { return sizeof(uint32_t) * ((size_t)T + (emit ? kEmitAuxWords + emit_stage_cap(T) : 0u)); }
 template <bool EMIT>
 __device__ __forceinline__ void
 bin_push_body(uint32_t N, const int *__restrict__ tl, const int *__restrict__ br, const float *__restrict__ depth, int ntw, int nth,
-              uint32_t T, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ tile_off, const uint32_t *__restrict__ ctrl,
-              unsigned long long *__restrict__ keys, uint32_t *s_tile) {
+              uint32_t T, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ tile_off,
+              const uint32_t *__restrict__ ctrl, unsigned long long *__restrict__ keys, uint32_t *s_tile) {
   if (EMIT && ctrl[1] != 0u) return;  // capacity exceeded: bin nothing
   const uint32_t chunk = blockIdx.x;
+  const uint32_t chunk_base = chunk * (uint32_t)kChunk;
   uint32_t *const crow = cnt + (size_t)chunk * T;
-  for (uint32_t t = threadIdx.x; t < T; t += (uint32_t)kPushThreads) s_tile[t] = EMIT ? tile_off[t] + crow[t] : 0u;
-  __syncthreads();
+  uint32_t *const s_wsum = s_tile + T, *const s_meta = s_wsum + 14, *const s_stage = s_wsum + kEmitAuxWords;  // (EMIT only)
+  const uint32_t stage_cap = emit_stage_cap(T);
   const int lane = lane_id();
-  const uint32_t stop = min(N, chunk * (uint32_t)kChunk + (uint32_t)kChunk);
+  uint32_t n_staged_tiles = 0, n_staged = 0;
+  if constexpr (EMIT) {
+    const uint32_t *const nrow = (chunk + 1u < gridDim.x) ? crow + T : tile_count;  // (gridDim.x = the number of chunks)
+    for (uint32_t t = threadIdx.x; t < T; t += (uint32_t)kPushThreads) s_tile[t] = nrow[t] - crow[t];
+    if (threadIdx.x < 2u) s_meta[threadIdx.x] = 0u;
+    __syncthreads();
+    // exclusive scan over the tiles: a contiguous block of tiles per thread, the threads' sums over the wavefront, the
+    // wavefronts' through LDS (c_t <= 2 048, T <= 8 192: no overflow)
+    const uint32_t per = (T + (uint32_t)kPushThreads - 1u) / (uint32_t)kPushThreads;
+    const uint32_t b = min(threadIdx.x * per, T), e = min(b + per, T);
+    uint32_t sum = 0;
+    for (uint32_t i = b; i < e; ++i) sum += s_tile[i];
+    uint32_t inc = sum;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t v = __shfl(inc, max(lane - d, 0), 64);
+      if (lane >= d) inc += v;
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if (lane == 63) s_wsum[wave] = inc;
+    __syncthreads();
+    uint32_t run = inc - sum;
+    for (uint32_t w = 0; w < wave; ++w) run += s_wsum[w];
+    uint32_t last_tile = 0, last_end = 0;
+    for (uint32_t i = b; i < e; ++i) {
+      const uint32_t c = s_tile[i];
+      if (run + c <= stage_cap) {  // staged: the cursor runs over the chunk's own layout
+        s_tile[i] = run;
+        last_tile = i + 1u; last_end = run + c;
+      } else {                           // does not fit any more: the cursor runs over the tile's segment
+        s_tile[i] = tile_off[i] + crow[i];
+      }
+      run += c;
+    }
+    if (last_tile != 0u) { atomicMax(&s_meta[0], last_tile); atomicMax(&s_meta[1], last_end); }
+    __syncthreads();
+    n_staged_tiles = s_meta[0]; n_staged = s_meta[1];
+  } else {
+    for (uint32_t t = threadIdx.x; t < T; t += (uint32_t)kPushThreads) s_tile[t] = 0u;
+    __syncthreads();
+  }
+  const uint32_t stop = min(N, chunk_base + (uint32_t)kChunk);
   auto visit = [&](int tile, uint32_t id, unsigned dbits) {
     const uint32_t pos = atomicAdd(&s_tile[tile], 1u);
-    if (EMIT) keys[pos] = ((unsigned long long)dbits << 32) | (unsigned long long)id;
+    if (EMIT) {
+      if ((uint32_t)tile < n_staged_tiles) {
+        if (pos < stage_cap) s_stage[pos] = ((uint32_t)tile << kEmitIdBits) | (id - chunk_base);  // (always: the count pass walked the same rectangles)
+      } else {
+        keys[pos] = ((unsigned long long)dbits << 32) | (unsigned long long)id;
+      }
+    }
   };
-  for (uint32_t i0 = chunk * (uint32_t)kChunk; i0 < stop; i0 += (uint32_t)kPushThreads) {  // (uniform trip count: ballots inside)
+  for (uint32_t i0 = chunk_base; i0 < stop; i0 += (uint32_t)kPushThreads) {  // (uniform trip count: ballots inside)
     const uint32_t i = i0 + threadIdx.x;
     int x0 = 0, y0 = 0, x1 = -1, y1 = -1;
     unsigned db = 0u;
@@ -723,26 +811,50 @@ bin_push_body(uint32_t N, const int *__restrict__ tl, const int *__restrict__ br
       }
     }
   }
-  if (!EMIT) {
-    __syncthreads();
+  __syncthreads();
+  if constexpr (!EMIT) {
     for (uint32_t t = threadIdx.x; t < T; t += (uint32_t)kPushThreads) crow[t] = s_tile[t];
+  } else {
+    // the staged tiles' cursors have ended on local_off[t + 1]: gdelta[t] = tile_off[t] + cnt[chunk][t] - local_off[t] in their place
+    constexpr int kPer = (int)kPushMaxTiles / kPushThreads;
+    uint32_t prev[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const uint32_t t = threadIdx.x + (uint32_t)(k * kPushThreads);
+      prev[k] = (t > 0u && t < n_staged_tiles) ? s_tile[t - 1u] : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const uint32_t t = threadIdx.x + (uint32_t)(k * kPushThreads);
+      if (t < n_staged_tiles) s_tile[t] = tile_off[t] + crow[t] - prev[k];
+    }
+    __syncthreads();
+#if defined(GSGEN_EMU_KNOBS)  // (the CPU emulator build of the tests: how many keys went through the staging array -- the lists cannot tell)
+    if (threadIdx.x == 0) gsgen_emu_emit_staged_keys += n_staged;
+#endif
+    for (uint32_t j = threadIdx.x; j < n_staged; j += (uint32_t)kPushThreads) {
+      const uint32_t w = s_stage[j];
+      const uint32_t id = chunk_base + (w & ((1u << kEmitIdBits) - 1u));
+      keys[j + s_tile[w >> kEmitIdBits]] = ((unsigned long long)__float_as_uint(depth[id]) << 32) | (unsigned long long)id;
+    }
   }
 }
 
 template <bool EMIT>
 __global__ void __launch_bounds__(kPushThreads)
 k_bin_push(uint32_t N, const int *__restrict__ tl, const int *__restrict__ br, const float *__restrict__ depth, int ntw, int nth,
-           uint32_t T, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ tile_off, const uint32_t *__restrict__ ctrl,
-           unsigned long long *__restrict__ keys) {
+           uint32_t T, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ tile_off,
+           const uint32_t *__restrict__ ctrl, unsigned long long *__restrict__ keys) {
   GS_PUSH_COUNTERS(s_tile);
-  bin_push_body<EMIT>(N, tl, br, depth, ntw, nth, T, cnt, tile_off, ctrl, keys, s_tile);
+  bin_push_body<EMIT>(N, tl, br, depth, ntw, nth, T, cnt, tile_count, tile_off, ctrl, keys, s_tile);
 }
 template <bool EMIT>
 __global__ void __launch_bounds__(kPushThreads)
 k_bin_push_views(uint32_t N, int ntw, int nth, uint32_t T, const GeoView *__restrict__ views) {
   GS_PUSH_COUNTERS(s_tile);
   const GeoView v = views[blockIdx.y];
-  bin_push_body<EMIT>(N, v.tl, v.br, v.depth, ntw, nth, T, v.cnt, v.tile_off, v.ctrl, v.keys, s_tile);
+  bin_push_body<EMIT>(N, v.tl, v.br, v.depth, ntw, nth, T, v.cnt, v.tile_count, v.tile_off, v.ctrl, v.keys, s_tile);
 }
 
 template <int P>
@@ -777,6 +889,7 @@ struct BinWs {
   uint32_t nchunks;
   size_t bytes;
 };
+// (tests/emit_runs.py: keys_region() repeats this layout to find the keys of an overflowing frame untouched -- and of a binned one written)
 static BinWs carve(void *base, uint32_t N, uint32_t D, uint32_t T, bool with_rects) {
   BinWs w{};
   size_t off = 0;
@@ -813,8 +926,8 @@ static int bin_and_sort(uint32_t N, uint32_t cap, uint32_t nth, uint32_t ntw, co
   if (N == 0) {
     if (hipError_t e = hipMemsetAsync(w.cnt, 0, sizeof(uint32_t) * (size_t)w.nchunks * T, s)) return (int)e;
   } else if (push) {
-    hipLaunchKernelGGL((k_bin_push<false>), dim3(w.nchunks), dim3(kPushThreads), sizeof(uint32_t) * T, s, N, tl, br, depth, (int)ntw, (int)nth, T, w.cnt,
-                       (const uint32_t *)nullptr, (const uint32_t *)nullptr, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL((k_bin_push<false>), dim3(w.nchunks), dim3(kPushThreads), push_lds_bytes(T, false), s, N, tl, br, depth, (int)ntw, (int)nth, T, w.cnt,
+                       (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (unsigned long long *)nullptr);
   } else {
     hipLaunchKernelGGL((k_bin_pull<false>), gpull, bpull, 0, s, N, tl, br, depth, (int)ntw, (int)nth, T,
                        w.cnt, w.wcnt, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
@@ -825,8 +938,8 @@ static int bin_and_sort(uint32_t N, uint32_t cap, uint32_t nth, uint32_t ntw, co
   hipLaunchKernelGGL(k_scan_order_tiles, dim3(1), dim3(kScanThreads), 0, s, T, w.tile_count, w.tile_off, w.ctrl, cap, total_out,
                      w.tile_order, report);
   if (N && push)
-    hipLaunchKernelGGL((k_bin_push<true>), dim3(w.nchunks), dim3(kPushThreads), sizeof(uint32_t) * T, s, N, tl, br, depth, (int)ntw, (int)nth, T, w.cnt,
-                       (const uint32_t *)w.tile_off, (const uint32_t *)w.ctrl, w.keys);
+    hipLaunchKernelGGL((k_bin_push<true>), dim3(w.nchunks), dim3(kPushThreads), push_lds_bytes(T, true), s, N, tl, br, depth, (int)ntw, (int)nth, T, w.cnt,
+                       (const uint32_t *)w.tile_count, (const uint32_t *)w.tile_off, (const uint32_t *)w.ctrl, w.keys);
   else if (N)
     hipLaunchKernelGGL((k_bin_pull<true>), gpull, bpull, 0, s, N, tl, br, depth, (int)ntw, (int)nth, T,
                        w.cnt, w.wcnt, w.tile_off, w.ctrl, w.keys);
@@ -860,6 +973,8 @@ int gsgen_internal_sort_segments(uint32_t T, const uint32_t *tile_off, const uin
 }
 
 const char *gsgen_version(void) { return "gsgen_hip 0.1 (gfx950)"; }
+
+uint32_t gsgen_emit_stage_capacity(void) { return kEmitStageWords; }
 
 int gsgen_selftest_reduce_scatter(uint32_t P, const float *in /*[64,P]*/, float *out /*[64]*/,
                                   gsgen_stream_t stream) {
@@ -967,14 +1082,14 @@ int gsgen_frame_geometry_batch_zero(uint32_t n_views, const gsgen_geometry_view 
     for (uint32_t b = 0; b < B; ++b)
       if (hipError_t e = hipMemsetAsync(gv[b].cnt, 0, sizeof(uint32_t) * (size_t)nchunks * T, s)) return (int)e;
   } else if (push) {
-    hipLaunchKernelGGL((k_bin_push_views<false>), gpush, bpush, sizeof(uint32_t) * T, s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
+    hipLaunchKernelGGL((k_bin_push_views<false>), gpush, bpush, push_lds_bytes(T, false), s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
   } else {
     hipLaunchKernelGGL((k_bin_pull_views<false>), gpull, bpull, 0, s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
   }
   hipLaunchKernelGGL(k_scan_chunks_views, dim3((T + kScanChunkTiles - 1) / kScanChunkTiles, B), dim3(256), 0, s, T, nchunks, (const GeoView *)dv);
   hipLaunchKernelGGL(k_scan_order_tiles_views, dim3(1, B), dim3(kScanThreads), 0, s, T, (const GeoView *)dv);
   if (N && push)
-    hipLaunchKernelGGL((k_bin_push_views<true>), gpush, bpush, sizeof(uint32_t) * T, s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
+    hipLaunchKernelGGL((k_bin_push_views<true>), gpush, bpush, push_lds_bytes(T, true), s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
   else if (N)
     hipLaunchKernelGGL((k_bin_pull_views<true>), gpull, bpull, 0, s, N, (int)ntw, (int)nth, T, (const GeoView *)dv);
   hipLaunchKernelGGL(k_sort_tiles_views, dim3(T * B), dim3(64 * kCoopWaves), 0, s, T, B, (const GeoView *)dv);

@@ -404,6 +404,11 @@ int gsgen_frame_geometry_batch_zero(uint32_t n_views, const gsgen_geometry_view 
  * The *_ordered variants of the SH compositing entry points take it (NULL = spatial order);
  * they are otherwise identical to gsgen_vol_render_sh / gsgen_vol_render_backward_sh. */
 const uint32_t *gsgen_frame_tile_order(void *workspace, uint32_t N, uint32_t D_cap, uint32_t n_tiles);
+/* How many (Gaussian, tile) keys of one 2 048-Gaussian chunk the batched binning groups by tile in LDS before it stores them
+ * (gsgen_amd/csrc/binning.hip, bin_push_body): a chunk with more keeps its leading tiles' keys there and stores the others one
+ * by one.  A constant of the build (images of more than 4 080 tiles stage less: the workgroup's LDS stays within 64 KB);
+ * the lists do not depend on it.  For tests that place a chunk on either side of it. */
+uint32_t gsgen_emit_stage_capacity(void);
 int gsgen_vol_render_sh_ordered(uint32_t N, uint32_t D, const float *mean, const float *cov,
                                 const float *sh_coeffs, const float *alpha, const int *start,
                                 const int *end, const int *gaussian_ids, float *out, const float *topleft,
