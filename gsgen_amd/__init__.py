@@ -9,6 +9,7 @@
     gsgen_amd.optim      one flat Adam step over the replicated parameters
     gsgen_amd.densify    the reference's densify / prune bookkeeping, identical on every rank (pure torch)
     gsgen_amd.io         the reference's checkpoint / .ply / .splat formats
+    gsgen_amd.loss       the fused SSIM + L1 / L2 image loss of utils/loss.py (ssim_loss, image_loss, get_image_loss, get_loss_fn)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
 There is no CPU implementation in this package: every entry point needs the HIP library and
@@ -23,6 +24,9 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name == "PairListOverflow":
         from .renderer import PairListOverflow
         return PairListOverflow
+    if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn"):
+        from . import loss
+        return getattr(loss, name)
     raise AttributeError(name)
 
 

@@ -27,6 +27,7 @@ SOURCES = {
     "legacy.hip": ["-ffp-contract=off"],
     "knn.hip": ["-ffp-contract=off"],  # dist2 bit-identical to an fp32 brute force (see the file header)
     "fps.hip": ["-ffp-contract=off"],  # d2 bit-identical to an fp32 NumPy loop (see the file header)
+    "loss.hip": ["-ffp-contract=off"],  # the filters' fmaf are explicit: the CPU emulator build rounds as the GPU does (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three
 # cross-file helpers used to be exported beside them)

@@ -50,7 +50,7 @@ extern "C" {
 
 typedef void *gsgen_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
-#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method */
+#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method, image loss window / channels */
 #define GSGEN_EINVAL (-3)       /* null pointer / inconsistent sizes */
 #define GSGEN_EWORKSPACE (-4)   /* workspace too small */
 
@@ -797,6 +797,31 @@ size_t gsgen_fps_workspace_bytes(uint32_t n_points, uint32_t dim, uint32_t n_sta
 int gsgen_fps(const float *points, uint32_t n_points, uint32_t dim, size_t cloud_stride, const int32_t *lengths,
               const int32_t *start_idx, uint32_t n_starts, uint32_t K, int32_t *idx_out, void *workspace, size_t workspace_bytes,
               int method, gsgen_stream_t stream);
+
+/* ---- fused SSIM + L1 / L2 image loss (gsgen_amd/csrc/loss.hip) --------------------------------------------------------
+ * replaces utils/loss.py:7-47: ssim_weight * kornia.losses.ssim_loss(out, gt, ws, "mean") + (1 - ssim_weight) * {mse | l1}(out, gt).
+ * out, gt: device fp32 [B,H,W,C], channels last, contiguous.  With p = (ws - 1) / 2, g[i] = exp(-(i - ws/2)^2 / 4.5) / sum and
+ * filt(x) the per-channel correlation of x, reflect-padded by p (the edge sample is not repeated), with g (x) g:
+ *   mu1 = filt(out), mu2 = filt(gt), s1 = filt(out^2) - mu1^2, s2 = filt(gt^2) - mu2^2, s12 = filt(out gt) - mu1 mu2,
+ *   s = (2 mu1 mu2 + 1e-4)(2 s12 + 9e-4) / ((mu1^2 + mu2^2 + 1e-4)(s1 + s2 + 9e-4) + 1e-12),
+ *   loss = ssim_weight * mean(clamp((1 - s) / 2, 0, 1)) + (1 - ssim_weight) * mean(base_kind 0: (out - gt)^2, 1: |out - gt|).
+ * ws odd in 3..11 and C in {1, 3}: a larger window, another C or base_kind is GSGEN_EUNSUPPORTED; an even window, ws < 3, H or
+ * W < p + 1 (torch's own reflect limit) or a null pointer: GSGEN_EINVAL; a workspace smaller than the query's answer for the same
+ * sizes: GSGEN_EWORKSPACE; a refused call enqueues nothing.  B * H * W == 0: 0 (success), nothing enqueued.
+ * forward: loss_out device float[3] = the loss, its ssim term, its base term (the two unweighted means).  With want_grad it also
+ *   saves three per-pixel derivative maps in the workspace (3 * B * H * W * C floats; gsgen_image_loss_workspace_bytes with
+ *   want_grad = 1), which the backward reads: call it with the same images, sizes, weight and workspace.
+ * backward: grad_out_image [B,H,W,C] = *grad_scale_dev * d loss / d out (overwritten; no gradient to gt).  The upstream scalar is
+ *   read on the device.
+ * Sums are reduced in a fixed order, no float atomics: loss and gradient are bit-identical from run to run.  Launch shapes depend
+ * on the sizes alone, no allocation, no host synchronisation: capturable, and a replay sees the values then in the buffers. */
+size_t gsgen_image_loss_workspace_bytes(uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t ws, int want_grad);
+int gsgen_image_loss_forward(const float *out, const float *gt, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t ws,
+                             float ssim_weight, int base_kind, int want_grad, float *loss_out, void *workspace, size_t workspace_bytes,
+                             gsgen_stream_t stream);
+int gsgen_image_loss_backward(const float *out, const float *gt, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t ws,
+                              float ssim_weight, int base_kind, const float *grad_scale_dev, float *grad_out_image, void *workspace,
+                              size_t workspace_bytes, gsgen_stream_t stream);
 
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
