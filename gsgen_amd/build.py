@@ -28,6 +28,7 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],  # dist2 bit-identical to an fp32 brute force (see the file header)
     "fps.hip": ["-ffp-contract=off"],  # d2 bit-identical to an fp32 NumPy loop (see the file header)
     "loss.hip": ["-ffp-contract=off"],  # the filters' fmaf are explicit: the CPU emulator build rounds as the GPU does (see the file header)
+    "marching_cubes.hip": ["-ffp-contract=off"],  # vertices bit-equal to the reference's unfused t * p2 + (1 - t) * p1 (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three
 # cross-file helpers used to be exported beside them)
@@ -39,7 +40,7 @@ def _newer(src, dst, extra=()):
         return True
     t = os.path.getmtime(dst)
     deps = [src, os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "composite_common.hpp"), os.path.join(CSRC, "knn_index.hpp"),
-            os.path.join(HERE, "..", "include", "gsgen_hip.h"), __file__, *extra]
+            os.path.join(CSRC, "mc_table.inc"), os.path.join(HERE, "..", "include", "gsgen_hip.h"), __file__, *extra]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -2,8 +2,8 @@
 
 For every point of a reso^3 lattice over [-L, L]^3 the reference searches the K + 1 nearest Gaussian centres (pytorch3d, in batches
 of 256 lattice points), drops the nearest and sums opacity * exp(-1/2 d^T Sigma^-1 d) over the K others.  Here one fused launch does
-the search and the sum: no index or distance array is written.  Marching cubes (PyMCubes, host code) and the file writing of
-`to_mesh` are not part of this package: feed the returned grid to them.
+the search and the sum: no index or distance array is written.  The rest of `to_mesh` is in gsgen_amd.mesh (marching cubes on the
+GPU, fed with the returned grid: density_mesh, mesh_from_ckpt) and gsgen_amd.io.write_obj.
 
 The functions take CUDA (HIP) tensors, run on the current stream without host synchronisation (get_density_val_grid_from_ckpt's
 `L < 0` takes the reference's own `.item()`), record no autograd graph, and can be captured by `torch.cuda.graph`.

@@ -1,7 +1,8 @@
 """On-disk formats of the reference: the trainer's checkpoint
 (trainer.py:255-266), the 17-field float32 `.ply` (utils/export.py:157-203) and the 32-byte-record
 `.splat` of the web viewer sorted by volume * opacity (utils/export.py:206-283).  Host code only,
-vectorised (the reference packs record by record with struct.pack); byte-identical output.
+vectorised (the reference packs record by record with struct.pack); byte-identical output.  Also the
+Wavefront `.obj` that `to_mesh` writes through mcubes.export_obj (utils/export.py:123-155).
 
 `params` is the dict the reference saves under "params": raw (pre-activation) tensors or arrays
 mean [N,3], qvec [N,4] (w,x,y,z), svec [N,3] (log scale), color [N,3] (logit), alpha [N] (logit).
@@ -113,3 +114,36 @@ def write_splat(path, params):
 
 def read_splat(path):
     return np.fromfile(path, SPLAT_DTYPE)
+
+
+# ---- .obj -----------------------------------------------------------------------------------------
+def write_obj(path, verts, tris):
+    """`v x y z` lines, then `f a b c` lines with 1-based vertex indices, no normals: the layout of mcubes.export_obj.  verts [V,3]
+    and tris [F,3] are tensors or arrays.  Coordinates are written with 9 significant digits, which identify a float32: read_obj
+    returns the same bits."""
+    v = verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts
+    t = tris.detach().cpu().numpy() if hasattr(tris, "detach") else tris
+    v, t = np.asarray(v, np.float32).reshape(-1, 3), np.asarray(t, np.int64).reshape(-1, 3)
+    if len(t) and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError(f"gsgen_amd.io.write_obj: triangle indices {t.min()}..{t.max()} for {len(v)} vertices")
+    with open(path, "w") as f:
+        f.write("".join("v %.9g %.9g %.9g\n" % (x, y, z) for x, y, z in v.astype(np.float64).tolist()))
+        f.write("".join("f %d %d %d\n" % (a, b, c) for a, b, c in (t + 1).tolist()))
+
+
+def read_obj(path):
+    """-> (verts float32 [V,3], tris int64 [F,3], 0-based) of a file of `v` and triangular `f` lines; `f` entries may carry
+    /texture/normal suffixes, which are dropped; other lines are ignored"""
+    v, t = [], []
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                v.append([float(x) for x in p[1:4]])
+            elif p[0] == "f":
+                if len(p) != 4:
+                    raise ValueError(f"gsgen_amd.io.read_obj: {path}: a face of {len(p) - 1} vertices (triangles only)")
+                t.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
+    return np.asarray(v, np.float64).reshape(-1, 3).astype(np.float32), np.asarray(t, np.int64).reshape(-1, 3)

@@ -823,6 +823,27 @@ int gsgen_image_loss_backward(const float *out, const float *gt, uint32_t B, uin
                               float ssim_weight, int base_kind, const float *grad_scale_dev, float *grad_out_image, void *workspace,
                               size_t workspace_bytes, gsgen_stream_t stream);
 
+/* ---- marching cubes over a dense lattice (gsgen_amd/csrc/marching_cubes.hip) -------------------------------------------
+ * replaces the PyMCubes call of utils/export.py:123-155.  grid: device fp32 [X][Y][Z], x slowest, contiguous (what
+ * gsgen_density_grid writes).  A lattice point is inside iff grid - thresh > 0 in fp32 (NaN: outside), the convention of the
+ * reference's own shap_e/rendering/mc.py; PyMCubes' tie-breaking at grid == thresh and its triangle order are not reproduced.
+ * verts [verts_capacity,3] fp32 in lattice index coordinates: one vertex per lattice edge whose end points differ in insideness,
+ *   all x-edges first, then y-, then z-edges, each in the raster order of the edge's lower point; with s1, s2 the values of
+ *   grid - thresh at the lower point p1 and at p2 = p1 + e_axis:  t = s1 / (s1 - s2), v = t * p2 + (1 - t) * p1, fp32, unfused.
+ * tris [tris_capacity,3] int32 vertex ids, 0..5 triangles per cube in cube raster order, normals from inside to outside.
+ * counts: device uint32[3] = {V, F, overflow}: always the true numbers of vertices and triangles; overflow = 1 when V >
+ *   verts_capacity or F > tris_capacity.  Then nothing is written past a capacity and the rows that fit are valid, but a written
+ *   triangle may name a vertex that was dropped: check the flag.  Capacities 0 (the pointers may then be NULL) only count.
+ * Any of X, Y, Z < 2 or X * Y * Z > 2^30: GSGEN_EUNSUPPORTED (the workspace query answers 0); a null grid, counts or workspace, a
+ * null output with a non-zero capacity, a capacity above 2^31 - 1: GSGEN_EINVAL; a workspace smaller than the query's answer:
+ * GSGEN_EWORKSPACE; a refused call enqueues nothing.  The workspace (4 bytes per lattice point + 32 per 1024 points) may be
+ * dirty and unaligned.  No atomics, no allocation, no host synchronisation, launch shapes from X, Y, Z alone: capturable, and the
+ * output is bit-identical from run to run.  F < 2^32 is assumed. */
+size_t gsgen_marching_cubes_workspace_bytes(uint32_t X, uint32_t Y, uint32_t Z);
+int gsgen_marching_cubes(const float *grid, uint32_t X, uint32_t Y, uint32_t Z, float thresh, float *verts, uint32_t verts_capacity,
+                         int32_t *tris, uint32_t tris_capacity, uint32_t *counts, void *workspace, size_t workspace_bytes,
+                         gsgen_stream_t stream);
+
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
  * lane owns (-1: duplicate holder); P in {8,16,32,64}. */
