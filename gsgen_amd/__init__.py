@@ -10,6 +10,7 @@
     gsgen_amd.densify    the reference's densify / prune bookkeeping, identical on every rank (pure torch)
     gsgen_amd.io         the reference's checkpoint / .ply / .splat formats
     gsgen_amd.loss       the fused SSIM + L1 / L2 image loss of utils/loss.py (ssim_loss, image_loss, get_image_loss, get_loss_fn)
+                         and its Pearson depth loss (depth_loss, pearson_depth_loss, pearson_depth_loss_terms)
     gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
@@ -25,7 +26,7 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name == "PairListOverflow":
         from .renderer import PairListOverflow
         return PairListOverflow
-    if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn"):
+    if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn", "depth_loss", "pearson_depth_loss", "pearson_depth_loss_terms"):
         from . import loss
         return getattr(loss, name)
     if name == "mesh":

@@ -28,6 +28,7 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],  # dist2 bit-identical to an fp32 brute force (see the file header)
     "fps.hip": ["-ffp-contract=off"],  # d2 bit-identical to an fp32 NumPy loop (see the file header)
     "loss.hip": ["-ffp-contract=off"],  # the filters' fmaf are explicit: the CPU emulator build rounds as the GPU does (see the file header)
+    "depth_loss.hip": ["-ffp-contract=off"],  # nothing fused: the CPU emulator build rounds as the GPU does (see the file header)
     "marching_cubes.hip": ["-ffp-contract=off"],  # vertices bit-equal to the reference's unfused t * p2 + (1 - t) * p1 (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three

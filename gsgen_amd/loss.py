@@ -13,6 +13,10 @@ Every function returns a 0-dim tensor; autograd reaches `out` only.  The loss ru
 torch's caching allocator and never synchronises with the host -- the backward reads the upstream gradient from device memory --
 so a forward + backward can be captured by `torch.cuda.graph` and replayed on new image values in the same tensors.  Loss and
 gradient are bit-identical from run to run (no float atomics).
+
+The depth loss of the image-conditioned step (utils/loss.py:50-66) is here too: `depth_loss` with the reference's signature,
+`pearson_depth_loss` and `pearson_depth_loss_terms` (gsgen_amd/csrc/depth_loss.hip; see the section further down).  It is capturable
+in the same way, with the mask as data, and differentiates with respect to both depth maps.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -147,3 +151,133 @@ def get_loss_fn(cfg):
     def fn(out, gt):
         return image_loss(out, gt, w, kind, ws)
     return fn
+
+
+# --- the Pearson depth loss (gsgen_amd/csrc/depth_loss.hip) ------------------------------------------------------------------
+# utils/loss.py:50-66, called at trainer.py:424-440 and :659-689: (1 / B) sum_b (1 - pearson(nan_to_num(pred_b)[m_b], gt_b[m_b])),
+# there a Python loop with a boolean gather per image (a host synchronisation) on top of torchmetrics.  Here: two launches forward,
+# one backward, no host synchronisation, capturable with the mask as data.  DESIGN.md ("Depth loss") has the definition and its one
+# deliberate difference: a degenerate image (fewer than two masked pixels, or all masked values of pred or of gt equal) contributes
+# 1 and a zero gradient where torchmetrics returns NaN; the per-image correlation reports NaN for it.
+def _depth_lib():
+    lib = _capi.load()
+    if not hasattr(lib, "depth_loss_forward"):
+        raise RuntimeError(f"{lib.path} was built without the depth loss kernels (gsgen_amd/csrc/depth_loss.hip): rebuild it "
+                           "(python -m gsgen_amd.build)")
+    return lib
+
+
+class _DepthLoss(torch.autograd.Function):
+    """pred [B,H,W], gt [B,H,W] or [1,H,W], mask uint8 [B,H,W] or [1,H,W] or None, all contiguous -> (loss 0-dim, corr [B]).
+    Only the loss is differentiable, to pred and gt."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mask):
+        B, P = pred.shape[0], pred.shape[1] * pred.shape[2]
+        dev = pred.device
+        lib = _depth_lib()
+        ctx.set_materialize_grads(False)
+        gt_stride = P if gt.shape[0] == B else 0   # (a batch of one against a batch of one: either)
+        mask_stride = 0 if mask is None or mask.shape[0] != B else P
+        nbytes = lib.depth_loss_workspace_bytes(B, P)
+        wsb = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        loss = torch.empty(1 + B, device=dev, dtype=torch.float32)
+        lib.depth_loss_forward(pred.data_ptr(), gt.data_ptr(), gt_stride, mask.data_ptr() if mask is not None else None, mask_stride, B, P,
+                               loss.data_ptr(), wsb.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(pred, gt, wsb, *(() if mask is None else (mask,)))
+            ctx.args = (B, P, gt_stride, mask_stride, nbytes)
+        total, corr = loss[0], loss[1:]
+        ctx.mark_non_differentiable(corr)
+        return total, corr
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, _g_corr):
+        if g_total is None:
+            return None, None, None
+        pred, gt, wsb, *rest = ctx.saved_tensors
+        mask = rest[0] if rest else None
+        B, P, gt_stride, mask_stride, nbytes = ctx.args
+        g = g_total.to(torch.float32).contiguous()  # (0-dim, on the device: the kernel reads it there)
+        grad_pred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        grad_gt = torch.empty_like(gt) if ctx.needs_input_grad[1] else None
+        _depth_lib().depth_loss_backward(pred.data_ptr(), gt.data_ptr(), gt_stride, mask.data_ptr() if mask is not None else None,
+                                         mask_stride, B, P, g.data_ptr(), grad_pred.data_ptr() if grad_pred is not None else None,
+                                         grad_gt.data_ptr() if grad_gt is not None else None, wsb.data_ptr(), nbytes,
+                                         torch.cuda.current_stream(pred.device).cuda_stream)
+        return grad_pred, grad_gt, None
+
+
+def _depth_images(name, t):
+    """-> t as [B, H, W]: [B,H,W,1] and [B,H,W] keep their batch; [H,W,1] and [H,W] are a batch of one (a 3-dim tensor whose last
+    size is 1 is read as [H,W,1])"""
+    if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3, 4):
+        raise ValueError(f"gsgen_amd.loss: {name} must be a [B, H, W, 1], [B, H, W], [H, W, 1] or [H, W] tensor, got shape "
+                         f"{tuple(getattr(t, 'shape', ())) or type(t)}")
+    if t.dim() == 4:
+        if t.shape[-1] != 1:
+            raise ValueError(f"gsgen_amd.loss: {name} must have one channel, got shape {tuple(t.shape)}")
+        return t[..., 0]
+    if t.dim() == 3:
+        return t[..., 0][None] if t.shape[-1] == 1 else t
+    return t[None]
+
+
+def _check_depth(pred_depth, depth_gt, mask):
+    """-> (pred [B,H,W], gt [B,H,W] or [1,H,W], mask [B,H,W] or [1,H,W] or None): views, nothing copied"""
+    pred, gt = _depth_images("pred_depth", pred_depth), _depth_images("depth_gt", depth_gt)
+    B, H, W = pred.shape
+    if gt.shape[1:] != (H, W) or gt.shape[0] not in (1, B):
+        raise ValueError(f"gsgen_amd.loss: pred_depth and depth_gt differ in shape: {tuple(pred_depth.shape)} and {tuple(depth_gt.shape)} "
+                         "(depth_gt may have a batch of one, or none, against a batched pred_depth)")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dim() not in (2, 3):
+            raise ValueError(f"gsgen_amd.loss: mask must be a [B, H, W] or [H, W] tensor, got shape "
+                             f"{tuple(getattr(mask, 'shape', ())) or type(mask)}")
+        if mask.dim() == 2:
+            mask = mask[None]
+        if mask.shape[1:] != (H, W) or mask.shape[0] not in (1, B):
+            raise ValueError(f"gsgen_amd.loss: a mask of shape {tuple(mask.shape)} does not fit depth images of shape {(B, H, W)}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise NotImplementedError(f"gsgen_amd.loss: mask must be bool or uint8, got {mask.dtype}")
+    if B == 0 or H * W == 0:
+        raise ValueError("gsgen_amd.loss: an empty batch or an empty image has no correlation")
+    if B > 65535:
+        raise NotImplementedError(f"gsgen_amd.loss: a batch of {B} depth images -- the kernels take up to 65535")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise NotImplementedError(f"gsgen_amd.loss: depth images must be float32, got {pred.dtype} and {gt.dtype}")
+    tensors = (pred, gt) if mask is None else (pred, gt, mask)
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError("gsgen_amd.loss: depth images and mask must be CUDA (HIP) tensors -- there is no CPU implementation")
+    if any(t.device != pred.device for t in tensors):
+        raise ValueError("gsgen_amd.loss: pred_depth, depth_gt and mask must be on one device")
+    return pred, gt, mask
+
+
+def pearson_depth_loss_terms(pred_depth, depth_gt, mask=None):
+    """-> (loss, corr [B]): the loss as pearson_depth_loss returns it and every image's Pearson correlation (float32, no gradient,
+    NaN for a degenerate image), from the same launch"""
+    pred, gt, mask = _check_depth(pred_depth, depth_gt, mask)
+    B = pred.shape[0]
+    if gt.shape[0] != B and gt.requires_grad:
+        gt = gt.expand(B, -1, -1)  # (made contiguous below: autograd sums the batch's gradients onto the one image)
+    if mask is not None:
+        mask = mask.detach().contiguous()
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)  # (the same bytes: a captured replay reads the caller's mask)
+    return _DepthLoss.apply(pred.contiguous(), gt.contiguous(), mask)
+
+
+def pearson_depth_loss(pred_depth, depth_gt, mask=None):
+    """(1 / B) sum_b (1 - r_b), r_b the Pearson correlation of nan_to_num(pred_depth[b]) and depth_gt[b] over the pixels where
+    mask[b] is true (all, without a mask), clamped to [-1, 1]; 0-dim float32.  Depth images are [B,H,W,1], [B,H,W], [H,W,1] or [H,W]
+    float32; depth_gt and mask ([B,H,W] or [H,W], bool or uint8) may have a batch of one, or none, against a batched pred_depth and
+    are then shared by stride, not copied.  Autograd reaches pred_depth and depth_gt, whichever requires a gradient (utils/loss.py's
+    callers pass the rendered depth on either side: trainer.py:432, :683)."""
+    return pearson_depth_loss_terms(pred_depth, depth_gt, mask)[0]
+
+
+def depth_loss(pearson, pred_depth, depth_gt, mask=None):
+    """utils/loss.py:50-66 with its signature: `pearson` (there a torchmetrics.PearsonCorrCoef) is ignored and may be None"""
+    return pearson_depth_loss(pred_depth, depth_gt, mask)

@@ -50,7 +50,7 @@ extern "C" {
 
 typedef void *gsgen_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
-#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method, image loss window / channels */
+#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method, image loss window / channels, depth loss B > 65535 */
 #define GSGEN_EINVAL (-3)       /* null pointer / inconsistent sizes */
 #define GSGEN_EWORKSPACE (-4)   /* workspace too small */
 
@@ -822,6 +822,37 @@ int gsgen_image_loss_forward(const float *out, const float *gt, uint32_t B, uint
 int gsgen_image_loss_backward(const float *out, const float *gt, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t ws,
                               float ssim_weight, int base_kind, const float *grad_scale_dev, float *grad_out_image, void *workspace,
                               size_t workspace_bytes, gsgen_stream_t stream);
+
+/* ---- Pearson depth loss (gsgen_amd/csrc/depth_loss.hip) ---------------------------------------------------------------
+ * replaces utils/loss.py:50-66: (1 / B) sum_b (1 - PearsonCorrCoef(nan_to_num(pred_b)[mask_b], gt_b[mask_b])), the loop over the
+ * batch with a boolean gather per image.  pred: device fp32 [B][n_pixels], contiguous.  gt: fp32, image b at gt + b *
+ * gt_image_stride (in elements); mask: uint8, non-zero = true, image b at mask + b * mask_image_stride, NULL = all true.  An
+ * image stride of 0 shares one gt / one mask across the batch.  Per image, over the masked pixels (n of them), with
+ * x = nan_to_num(pred) (NaN -> 0, +-Inf -> +-FLT_MAX) and y = gt as it is:
+ *   xm = sum x / n, ym = sum y / n, Sxx = sum (x - xm)^2, Syy = sum (y - ym)^2, Sxy = sum (x - xm)(y - ym),
+ *   r = clamp(Sxy / sqrt(Sxx Syy), -1, 1),  loss = (1 / B) sum_b (1 - r_b).
+ * A DEGENERATE image -- n < 2, all masked x equal, or all masked y equal (decided exactly, from the minimum and maximum) -- is
+ * where the reference returns NaN; here it contributes 1 (r = 0) and a zero gradient.  A NaN in gt under the mask is not
+ * sanitised: the loss is NaN.
+ * forward: loss_out device float[1 + B] = the loss, then r_b per image (NaN for a degenerate image).  It saves the per-image
+ *   moments in the workspace, which the backward reads: call it with the same arrays, sizes and workspace.
+ * backward: grad_pred [B][n_pixels] and grad_gt (laid out as gt is) = *grad_scale_dev * d loss / d pred, d loss / d gt; either may be
+ *   NULL; both are overwritten, with zeros outside the mask, for a degenerate image, where the clamp is active and (grad_pred
+ *   only) where pred was not finite.  The upstream scalar is read on the device.
+ * B > 65535: GSGEN_EUNSUPPORTED (the workspace query answers 0); a null pred, gt, loss_out, grad_scale_dev or workspace, or a
+ * grad_gt with gt_image_stride == 0 and B > 1: GSGEN_EINVAL; a workspace smaller than the query's answer: GSGEN_EWORKSPACE; a
+ * refused call enqueues nothing.  B * n_pixels == 0: 0 (success), nothing enqueued.  The workspace (80 bytes per 4096 pixels of an
+ * image + 48 per image) may be dirty and unaligned: there is no fill launch.  Moments are summed in fp64 about a value of the data
+ * and merged in a fixed order, no float atomics: loss and gradients are bit-identical from run to run.  Two launches forward, one
+ * backward, their shapes from B and n_pixels alone, no allocation, no host synchronisation: capturable, and a replay sees the
+ * values then in the buffers, the mask included. */
+size_t gsgen_depth_loss_workspace_bytes(uint32_t B, uint32_t n_pixels);
+int gsgen_depth_loss_forward(const float *pred, const float *gt, size_t gt_image_stride, const uint8_t *mask, size_t mask_image_stride,
+                             uint32_t B, uint32_t n_pixels, float *loss_out, void *workspace, size_t workspace_bytes,
+                             gsgen_stream_t stream);
+int gsgen_depth_loss_backward(const float *pred, const float *gt, size_t gt_image_stride, const uint8_t *mask, size_t mask_image_stride,
+                              uint32_t B, uint32_t n_pixels, const float *grad_scale_dev, float *grad_pred, float *grad_gt,
+                              void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
 
 /* ---- marching cubes over a dense lattice (gsgen_amd/csrc/marching_cubes.hip) -------------------------------------------
  * replaces the PyMCubes call of utils/export.py:123-155.  grid: device fp32 [X][Y][Z], x slowest, contiguous (what
