@@ -11,6 +11,8 @@
     gsgen_amd.io         the reference's checkpoint / .ply / .splat formats
     gsgen_amd.loss       the fused SSIM + L1 / L2 image loss of utils/loss.py (ssim_loss, image_loss, get_image_loss, get_loss_fn)
                          and its Pearson depth loss (depth_loss, pearson_depth_loss, pearson_depth_loss_terms)
+    gsgen_amd.background the learned MLP background of conf/renderer/mlp_bg.yaml fused with its composite (MLPBackground, mlp_background,
+                         mlp_background_images, mlp_background_over)
     gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
@@ -29,6 +31,9 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn", "depth_loss", "pearson_depth_loss", "pearson_depth_loss_terms"):
         from . import loss
         return getattr(loss, name)
+    if name in ("MLPBackground", "mlp_background", "mlp_background_images", "mlp_background_over"):
+        from . import background
+        return getattr(background, name)
     if name == "mesh":
         import importlib
         return importlib.import_module(".mesh", __name__)

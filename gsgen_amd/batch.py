@@ -471,6 +471,14 @@ class BatchRenderer:
         self._upload(cam_infos, c2ws, frustum_radius, tile_radius)
         self._cis = list(cam_infos)
 
+    def camera_blocks(self, cam_infos, c2ws, frustum_radius=6.0, tile_radius=6.0):
+        """-> the batch's camera blocks in device memory, [B, 68] float32 rows 272 bytes apart (floats 0..11 the c2w rows, 12..15 fx fy
+        cx cy), uploaded on the current stream as render / render_heads upload them: for a kernel that needs the cameras in front of the
+        render (gsgen_amd.background).  The rows are the renderer's own and hold the NEXT upload's cameras after it.  Inside a capture a
+        device_cameras renderer uploads nothing: the rows are what upload_cameras put there."""
+        self._check_batch(cam_infos)
+        return self._upload(cam_infos, c2ws, frustum_radius, tile_radius)
+
     def _mask_table(self, B):
         """void*[B] of the slots' visibility masks (they never move): built once per batch size"""
         t = self._ptr_tabs.get(B)

@@ -20,9 +20,9 @@ optimizer / update / densify / prune / log / auxiliary_loss / bg(rays_d) exist s
 drop-in (gsgen_amd.install_as_gs) stays available for code that calls the 23 names directly, at the reference's serial shape
 (bench.py reports both: `dropin_gs_surface` against `model_surface`).
 
-What is NOT carried over (raises NotImplementedError when configured or called): normal_as_rgb, pbr / specular shading, MLPBackground
-(tinycudann), overrides of anything but `color`, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of
-update().  Penalty losses and compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
+What is NOT carried over (raises NotImplementedError when configured or called): normal_as_rgb, pbr / specular shading, overrides of
+anything but `color`, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of update().  The learned
+MLPBackground (background.type "mlp", tinycudann in the reference) runs on gsgen_amd.background.  Penalty losses and compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
 The densify / prune policies themselves live in gsgen_amd.densify (this class delegates; AdaptiveControl is the multi-rank form on a
 FusedAdam), the flat-buffer optimiser in gsgen_amd.optim.
 """
@@ -125,7 +125,9 @@ def schedule_value(spec, step, max_steps=None):
 class _Background(nn.Module):
     """gs/backgrounds.py: `fixed` (a constant colour held as a Parameter, :33-45), `random` (one torch.rand(3) per camera while
     training, black in eval, :48-70 -- drawn from torch's CPU generator exactly as the reference draws it, one draw per camera
-    in batch order, so a seeded run sees the same colours), `learned_const` (:73-85).  -> [B, 1, 1, 3] for the batch."""
+    in batch order, so a seeded run sees the same colours), `learned_const` (:73-85).  -> [B, 1, 1, 3] for the batch.
+    `mlp` (:88-114) is a colour per pixel: bg(rays_d), images(cams, B, H, W) and over(rgb, opacity, cams) on gsgen_amd.background; its
+    768 parameters are `mlp.params`, the reference's state-dict key."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -137,8 +139,15 @@ class _Background(nn.Module):
             self.bg_color = nn.Parameter(torch.tensor(list(_get(cfg, "color")), dtype=torch.float32))
         elif self.type == "learned_const":
             self.bg_color = nn.Parameter(torch.tensor(list(_get(cfg, "initial_color", [0.5, 0.5, 0.5])), dtype=torch.float32))
+        elif self.type == "mlp":
+            # gs/backgrounds.py:88-114 on gsgen_amd.background (the reference's needs tinycudann): a colour per PIXEL, so the batched
+            # forward goes through images() / over() below and not through forward(B)
+            from .background import MLPBackground
+            if self.random_aug:
+                raise NotImplementedError("gsgen_amd.model: background.random_aug with type 'mlp' (conf/renderer/mlp_bg.yaml does not use it)")
+            self.mlp = MLPBackground(None).mlp  # (the state dict key is `mlp.params`, as the reference's)
         elif self.type != "random":
-            raise NotImplementedError(f"gsgen_amd.model: background type {self.type!r} (MLPBackground needs tinycudann; pass the "
+            raise NotImplementedError(f"gsgen_amd.model: background type {self.type!r} (known: fixed, random, learned_const, mlp; pass the "
                                       "colours yourself through BatchRenderer.render_heads(bg_rgb=...))")
         # a captured step (gsgen_amd.graph.CapturedStep, model.device_cameras): the colours drawn on the host live in ONE device tensor
         # that the captured launches read; a forward enqueued into a capture draws nothing, refresh() draws for the next replay
@@ -148,6 +157,12 @@ class _Background(nn.Module):
     def forward(self, B, device=None):
         """B cameras -> [B, 1, 1, 3] (what the batched forward composites); or, called as the reference calls it -- bg(rays_d) with
         rays_d [H, W, 3], gs/gaussian_splatting.py:1321 -- -> [H, W, 3] for one camera"""
+        if self.type == "mlp":
+            if not isinstance(B, torch.Tensor):
+                raise TypeError("gsgen_amd.model: an mlp background has a colour per pixel: call bg(rays_d), bg.images(cams, B, H, W) or "
+                                "bg.over(rgb, opacity, cams)")
+            from .background import mlp_background
+            return mlp_background(self.mlp.params, B)
         if isinstance(B, torch.Tensor):
             rays = B
             return self.forward(1, rays.device).view(1, 1, 3).expand(rays.shape[0], rays.shape[1], 3).to(rays.dtype)
@@ -171,6 +186,16 @@ class _Background(nn.Module):
             rnd = torch.stack([torch.rand(3) for _ in range(B)]).to(cols).view(B, 1, 1, 3)
             return torch.where(pick.view(B, 1, 1, 1), rnd, cols)
         return self._colours(B, device)
+
+    def images(self, cams, B, H, W):
+        """type 'mlp': -> [B, H, W, 3], the learned colour of every pixel of the B cameras whose blocks are the rows of cams"""
+        from .background import mlp_background_images
+        return mlp_background_images(self.mlp.params, cams[:B], H, W)
+
+    def over(self, rgb, opacity, cams):
+        """type 'mlp': -> rgb + (1 - opacity) * bg in one launch (gsgen_amd.background.mlp_background_over)"""
+        from .background import mlp_background_over
+        return mlp_background_over(self.mlp.params, rgb, opacity, cams)
 
     def _colours(self, B, device):
         if self.type == "random":
@@ -342,8 +367,15 @@ class GaussianSplattingRenderer(nn.Module):
             stats = _Stats(self.max_radii2d, self.mean_2d_grad_accum if self.densify_enabled else None,
                            self.cnt if self.densify_enabled else None)
         self.bg.static = self.device_cameras
-        bg = self.bg(B, self.mean.device)
         fr = 0.0 if self.skip_frustum_culling else self.frustum_culling_radius
+        mlp_bg = self.bg.type == "mlp"
+        if mlp_bg:
+            # a learned colour per pixel (gsgen_amd.background), from the renderer's own camera blocks -- with device_cameras the
+            # device ones, so a captured step's replay draws the background of the cameras then in place, with no upload of its own
+            cams = br.camera_blocks(cis, c2ws, fr, self.tile_culling_radius)
+            bg = self.bg.images(cams, B, H, W) if rgb_only else None
+        else:
+            bg = self.bg(B, self.mean.device)
         if color is not None and (not isinstance(color, torch.Tensor) or tuple(color.shape) != (self.N, 3)):
             raise ValueError(f"gsgen_amd.model: a colour override must be a [{self.N}, 3] tensor, got {getattr(color, 'shape', type(color))}")
         if rgb_only:
@@ -360,6 +392,10 @@ class GaussianSplattingRenderer(nn.Module):
                                                         thresh=self.T_thresh, frustum_radius=fr, tile_radius=self.tile_culling_radius,
                                                         detach_depth=self.depth_detach, stats=stats, z_var=True,
                                                         activations=acts)
+        if mlp_bg:
+            # rgb + (1 - opacity) bg: opacity = sum alpha_i T_i telescopes to 1 - T, so this is gs/renderer.py:1182's rgb + T bg up to
+            # rounding, and the Gaussians receive the background's d T / d alpha term through the opacity head's gradient
+            rgb = self.bg.over(rgb, opacity, cams)
         return {"rgb": rgb, "depth": depth, "opacity": opacity, "z_var": z_var}
 
     def render_one(self, c2w, camera_info, use_bg=True, rgb_only=False, overrides=None, return_T=False):
@@ -674,4 +710,7 @@ class GaussianSplattingRenderer(nn.Module):
         return density_grid(self.mean, self.qvec, self.svec, self.alpha, L, reso, K, True)
 
     def get_params_for_save(self):  # gs/gaussian_splatting.py:294-311 (the five raw fields; gsgen_amd.io writes them)
-        return {k: getattr(self, k).detach() for k in self.raw_fields}
+        params = {k: getattr(self, k).detach() for k in self.raw_fields}
+        if self.bg.type == "mlp":  # (:302: the learned background's state dict, key `mlp.params`)
+            params["bg"] = self.bg.state_dict()
+        return params

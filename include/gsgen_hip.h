@@ -50,7 +50,7 @@ extern "C" {
 
 typedef void *gsgen_stream_t; /* hipStream_t; NULL = the legacy default stream */
 
-#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method, image loss window / channels, depth loss B > 65535 */
+#define GSGEN_EUNSUPPORTED (-2) /* tile_size not in 1 .. 32 (16 only: batched / segmented / fused), C not in 1..4, kNN K not in 1..32, FPS dim / method, image loss window / channels, depth loss B > 65535, MLP background B H W > 2^31 */
 #define GSGEN_EINVAL (-3)       /* null pointer / inconsistent sizes */
 #define GSGEN_EWORKSPACE (-4)   /* workspace too small */
 
@@ -874,6 +874,37 @@ size_t gsgen_marching_cubes_workspace_bytes(uint32_t X, uint32_t Y, uint32_t Z);
 int gsgen_marching_cubes(const float *grid, uint32_t X, uint32_t Y, uint32_t Z, float thresh, float *verts, uint32_t verts_capacity,
                          int32_t *tris, uint32_t tris_capacity, uint32_t *counts, void *workspace, size_t workspace_bytes,
                          gsgen_stream_t stream);
+
+/* ---- learned MLP background, fused with its composite (gsgen_amd/csrc/background.hip) -----------------------------------
+ * replaces gs/backgrounds.py:88-114 (tcnn.NetworkWithInputEncoding: SphericalHarmonics degree 3 -> FullyFusedMLP ReLU 16 x 2) and
+ * the composite of gs/renderer.py:1182.  DESIGN.md ("MLP background") has the definition, a reading of tinycudann that no reference
+ * run pins.  Per pixel p = (b, y, x) of a [B][H][W] batch, in fp32:
+ *   d = R_b ((x - cx) / fx, (y - cy) / fy, 1), e = 2 d - 1, u = (the 9 SH terms of degree < 3 at e, then seven ones),
+ *   h1 = relu(W0 u), h2 = relu(W1 h1), o = (W2 h2)[0..2], bg = nan_to_num(sigmoid(o))  (a NaN becomes 0).
+ * params: device float[768] = W0 | W1 | W2, each [16 out][16 in] row-major; rows 3..15 of W2 are never read.
+ * Directions come from ONE of: cams -- per-view camera blocks in device memory, view b at cams + b * cam_stride_bytes (a multiple
+ *   of 4, at least 64), floats 0..11 the c2w rows, 12..15 fx fy cx cy: what gsgen_pack_camera writes (BatchRenderer's blocks are
+ *   272 bytes apart; a stand-alone caller may pack [B][16]); or dirs -- device float[B H W][3], used as d.  The other is NULL.
+ * forward: out [B][H][W][3] = bg, or rgb_in + (1 - opacity) * bg when rgb_in [B][H][W][3] and opacity [B][H][W] are given (both
+ *   or neither).  One launch.
+ * backward: recomputes the forward per pixel (nothing per-pixel was saved).  grad_out [B][H][W][3] is the upstream gradient of
+ *   out, read on the device.  grad_params float[768] is overwritten; the entries of W2's rows 3..15 are exactly 0.  With opacity
+ *   given (the composite form) the background's gradient carries the factor (1 - opacity), and grad_opacity [B][H][W] (optional)
+ *   = -sum_c grad_out_c bg_c.  The gradient of rgb_in is grad_out itself.  A pixel whose o is not finite contributes nothing to
+ *   grad_params.  Two launches: per-workgroup partial sums on the exact fp32 MFMA, then a fixed-order sum; no float atomics, so
+ *   the result is bit-identical from run to run.
+ * B * H * W > 2^31: GSGEN_EUNSUPPORTED (the workspace query answers 0); a null params / out / grad_out / grad_params / workspace,
+ * both or neither of cams and dirs, a bad cam_stride_bytes, rgb_in without opacity or the reverse, grad_opacity without opacity:
+ * GSGEN_EINVAL; a workspace smaller than the query's answer: GSGEN_EWORKSPACE; a refused call enqueues nothing.  B * H * W == 0: 0
+ * (success), nothing enqueued.  The workspace (3 KB per backward workgroup, at most 1024 of them) may be dirty and unaligned.  No
+ * allocation, no host synchronisation, launch shapes from B, H, W alone: capturable, and a replay reads the parameters, camera
+ * blocks and gradients then in the buffers. */
+size_t gsgen_mlp_background_workspace_bytes(uint32_t B, uint32_t H, uint32_t W);
+int gsgen_mlp_background_forward(const float *params, const void *cams, size_t cam_stride_bytes, const float *dirs, uint32_t B,
+                                 uint32_t H, uint32_t W, const float *rgb_in, const float *opacity, float *out, gsgen_stream_t stream);
+int gsgen_mlp_background_backward(const float *params, const void *cams, size_t cam_stride_bytes, const float *dirs, uint32_t B,
+                                  uint32_t H, uint32_t W, const float *opacity, const float *grad_out, float *grad_params,
+                                  float *grad_opacity, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
 
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
