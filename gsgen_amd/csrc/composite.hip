@@ -210,6 +210,8 @@ template <bool BATCH> struct ViewPack {
 template <> struct ViewPack<false> {
   __host__ __device__ const CompParams *table() const { return nullptr; }
 };
+// (a kernel's arguments -- its own block + the pack -- must fit the 4 KB the runtime passes them in)
+static_assert(sizeof(CompParams) + sizeof(ViewPack<true>) <= 4096, "a batched launch's kernel arguments");
 // BATCH: one launch renders B cameras, each workgroup taking its camera's parameters from plist[view]
 // (the kernel-argument table) instead of p_arg -- a single launch's tail (the never-saturating
 // sparse tiles) is then paid once per batch instead of once per camera.  The grid is 1-D, B x the
@@ -490,10 +492,18 @@ __device__ __forceinline__ uniform_floats uniform_pointer(const float *q) {
                           (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u));
 }
 __device__ __forceinline__ float rsqrt_fast(float v) { return __builtin_amdgcn_rsqf(v); }
+// one word another launch wrote, at an address that is the same in every lane: a scalar load whatever this kernel stores elsewhere
+__device__ __forceinline__ uint32_t uniform_word(const uint32_t *q) {
+  typedef const uint32_t __attribute__((address_space(4))) *uniform_words;
+  const uintptr_t u = (uintptr_t)q;
+  return *(uniform_words)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) |
+                          (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u));
+}
 #else
 typedef const float *uniform_floats;  // (the host pass of hipcc and the CPU emulator build)
 __device__ __forceinline__ uniform_floats uniform_pointer(const float *q) { return q; }
 __device__ __forceinline__ float rsqrt_fast(float v) { return 1.0f / sqrtf(v); }
+__device__ __forceinline__ uint32_t uniform_word(const uint32_t *q) { return *q; }
 #endif
 // One pixel's three logits -log2(e) * (sh_c . Y(pixel)), |s| <= 40 (as poly_transform keeps the polynomial's: the product of three
 // denominators stays finite).  NOT inlined, and written to stay small: the polynomial kernels' register budgets are their entry
@@ -600,7 +610,12 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
   if (!block_tile(p, tx, ty, bid)) return;  // uniform over the workgroup
   const int tile = ty * p.ntw + tx;
   const int st = p.start[tile];
-  const int n = (st < 0) ? 0 : (p.end[tile] - st);
+  // The walk summary (composite_common.hpp, kWalkWords) is kept by the shape whose wavefront IS the tile: the batched polynomial
+  // kernel of an unsegmented launch.  There the list's length is moved to a scalar register, so that the loops over it -- and the
+  // summary's words, which are built inside them and stored behind them -- stay on the scalar unit.
+  constexpr bool SUMMARY = POLY && PPL == 4 && !PERSIST && !TRACK;
+  const int n_list = (st < 0) ? 0 : (p.end[tile] - st);
+  const int n = SUMMARY ? __builtin_amdgcn_readfirstlane(n_list) : n_list;
   const int t = tile_thread_index<PERSIST>();
   const int lx = t & 15, ly0 = t >> 4;
   const int gx = tx * kTile + lx;
@@ -690,10 +705,18 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
   const bool seg_out = p.nseg > 1 && p.ckpt != nullptr;
   const bool track_stop = TRACK && p.stop != nullptr;
 
+  // The walk summary: this tile's record.  A batch's two words are built in scalar registers and stored once.
+  // The length of the walk is stored with them, each staged batch overwriting the last one's: nothing but the loop counters is
+  // carried from entry to entry.
+  uint32_t *const walk_rec = (SUMMARY && p.walk != nullptr) ? p.walk + (size_t)tile * kWalkWords : nullptr;
+  static_assert(!SUMMARY || KB == 32, "a staged batch is a word of the summary");
+
   uint32_t exact_mask = 0u;  // POLY: the staged batch's splats of the per-entry exact tier
   uint32_t tay_mask = 0u;    // POLY: ... and those of the Taylor tier (no exponential per pixel: composite_common.hpp)
-  for (int base = 0; base < n; base += KB) {
+  int base = 0;
+  for (; base < n; base += KB) {
     const int nb = min(KB, n - base);
+    uint32_t walk_con = 0u, walk_guard = 0u;
     if (base > 0) __syncthreads();  // everyone is done with the previous batch
     stage_batch<MODE, CB, NT, KB, true, !POLY>(S, p, st + base, nb);
     if constexpr (POLY) {
@@ -726,7 +749,8 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
       __syncthreads();
     }
 
-    for (int g = 0; g < nb; ++g) {
+    int g = 0;  // (behind the loop: the number of this batch's entries the loop reached)
+    for (; g < nb; ++g) {
       bool any_alive = false;
 #pragma unroll
       for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
@@ -742,30 +766,23 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
       const float r_mx = S.mx[g], r_my = S.my[g], r_a = S.a[g], r_c0 = S.c0[g], r_c1 = S.c1[g], r_c2 = S.c2[g],
                   r_c3 = S.c3[g], r_p0 = S.p0[g];
       const float x = px - r_mx;
-      // G2 / ag2: the Gaussian and a G, ZEROED where the pixel does not take part (skip threshold, or not alive)
-      v2f G2[NP], ag2[NP];
+      // G2 / ag2: the Gaussian and a G, ZEROED where the pixel does not take part (skip threshold, not alive, or radial < 0)
+      v2f G2[NP], ag2[NP], q2[NP];
       bool any_con = false;
-      float guard_dist = 0.0f;
 #pragma unroll
       for (int jp = 0; jp < NP; ++jp) {
-        G2[jp] = gauss_sh_pair(r_c0, r_c1, r_c2, r_c3, r_p0, x, py2[jp] - splat2(r_my));
+        G2[jp] = gauss_sh_pair(r_c0, r_c1, r_c2, r_c3, r_p0, x, py2[jp] - splat2(r_my), q2[jp]);
         ag2[jp] = splat2(r_a) * G2[jp];
-        {
-          // the lane's smallest distance to the threshold (dead pixels included: a spurious trip re-tests per pixel)
-          const v2f dist = ag2[jp] - splat2(kMinAlpha);
-          const float dmin = fminf(fabsf(dist[0]), fabsf(dist[1]));
-          guard_dist = jp == 0 ? dmin : fminf(guard_dist, dmin);
-        }
       }
-      const bool any_guard = guard_dist <= kMinAlpha * kGuardTol;
       // within rounding of the skip threshold the reference's arithmetic decides (as gauss_eval); one wave-uniform
       // test for all the lane's pixels, almost never taken
-      if (wave_any(any_guard)) {
+      const uint32_t guarded = sh_guard_trips<NP>(ag2, q2);
+      if (guarded != 0u) {
 #pragma unroll
         for (int jp = 0; jp < NP; ++jp)
 #pragma unroll
           for (int e = 0; e < 2; ++e)
-            if (alive(2 * jp + e) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
+            if (alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
               G2[jp][e] = gauss_ref_f32(r_mx, r_my, r_c0, r_c1, r_c2, r_c3, px, py2[jp][e]);
               ag2[jp][e] = r_a * G2[jp][e];
             }
@@ -774,7 +791,8 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
       for (int jp = 0; jp < NP; ++jp)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const bool con = alive(2 * jp + e) && !(ag2[jp][e] < kMinAlpha);
+          // (radial < 0: gauss_eval's G = 0, which no pixel contributes with -- a term of the mask, see gauss_sh_pair)
+          const bool con = alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && !(ag2[jp][e] < kMinAlpha);
           G2[jp][e] = con ? G2[jp][e] : 0.0f;
           if constexpr (!POLY) ag2[jp][e] = con ? ag2[jp][e] : 0.0f;
           any_con |= con;
@@ -785,7 +803,12 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
           ag2[jp] = splat2(r_a) * G2[jp];
         }
       }
-      if (!wave_any(any_con)) continue;  // nobody in the wave sees this Gaussian
+      const uint32_t contributed = wave_any_word(any_con);
+      if constexpr (SUMMARY) {  // (scalar: two shifts and two ORs per entry)
+        walk_con |= contributed << g;
+        walk_guard |= guarded << g;
+      }
+      if (contributed == 0u) continue;  // nobody in the wave sees this Gaussian
 
       const float *cg = POLY ? &Ws[g * 3 * kPolyStride] : &S.col[g * TR::NCOLP];
       v2f w2[NP];
@@ -859,11 +882,31 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
         for (int jp = 0; jp < NP; ++jp) Tr2[jp] = Tr2[jp] * one_minus2(ag2[jp]);
       }
     }
+    if constexpr (SUMMARY) {
+      if (walk_rec != nullptr && t == 0) {
+        walk_rec[0] = (uint32_t)(base + g);
+        if (base < kWalkK * KB) {
+          walk_rec[1 + base / KB] = walk_con;
+          walk_rec[1 + kWalkK + base / KB] = walk_guard;
+        }
+      }
+    }
+    (void)walk_con; (void)walk_guard; (void)g;
     bool any_alive = false;
 #pragma unroll
     for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
-    if (__syncthreads_or((int)any_alive) == 0) break;  // whole tile saturated: stop staging
+    int some_alive = __syncthreads_or((int)any_alive);
+    if constexpr (SUMMARY) some_alive = __builtin_amdgcn_readfirstlane(some_alive);  // (`base` is read behind the loop: a uniform exit)
+    if (some_alive == 0) break;  // whole tile saturated: stop staging
   }
+  if constexpr (SUMMARY) {
+    if (walk_rec != nullptr) {
+      // zeros in the words of the batches that were never staged: every word of the record is written
+      const int staged = min(base / KB + 1, (n + KB - 1) / KB);  // (left by the break: base is the last staged batch's)
+      if (t < 2 * kWalkK && (t & (kWalkK - 1)) >= staged) walk_rec[1 + t] = 0u;
+    }
+  }
+  (void)walk_rec;
 
 #pragma unroll
   for (int j = 0; j < PPL; ++j) {
@@ -1311,12 +1354,13 @@ struct BwdShVecShared {
 // anyway -- (Mx, My) into grad_mean, (Mxx, Mxy, Myy) into grad_cov[0..2] -- and the projection backward scales them by 1 / det and
 // 0.5 / det^2 per (view, Gaussian) (geometry.hip, moments_to_grads_sh): 7 packed operations per pixel pair instead of 13, one
 // atomic per entry less (grad_cov[2] = grad_cov[1] is formed there too).
-template <int CB, int PPL, int NB, bool PERSIST = false, bool MOM = false>
+template <int CB, int PPL, int NB, bool PERSIST = false, bool MOM = false, bool HANDOFF = false>
 __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, uint32_t bid, uint32_t grid,
                                                           BwdShVecShared<CB, PPL, (NB > 0)> &sm) {
   static_assert(PPL == 4 || PPL == 2, "pixel pairs: 2 or 4 pixels per lane");
   constexpr bool POLY = NB > 0;
   static_assert(!POLY || (NB == kPolyNB && CB == 4 && PPL == 4), "polynomial basis: SH degree 3, one wavefront per tile");
+  static_assert(!HANDOFF || (POLY && !PERSIST), "the walk summary is the batched polynomial kernels'");
   constexpr int MODE = MODE_SH;
   using TR = Traits<MODE, CB>;
   constexpr int NT = 256 / PPL, ROWS = NT / 16, NP = PPL / 2;
@@ -1335,7 +1379,8 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
   if (!block_tile(p, tx, ty, bid % tiles_grid)) return;  // uniform over the workgroup
   const int tile = ty * p.ntw + tx;
   const int st = p.start[tile];
-  const int n = (st < 0) ? 0 : (p.end[tile] - st);
+  const int n_list = (st < 0) ? 0 : (p.end[tile] - st);
+  const int n = HANDOFF ? __builtin_amdgcn_readfirstlane(n_list) : n_list;  // (as the forward that keeps the summary: scalar loop bounds)
   if (n == 0 || n < p.n_lo || n >= p.n_hi) return;
   if constexpr (POLY) {  // per-tile routing: the forward sent this tile to the exact kernel (CompParams::tile_flags)
     if (p.tile_flags != nullptr && p.tile_flags[tile] != 0) return;
@@ -1456,291 +1501,322 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
   }
   auto alive = [&](int j) { return !(Tr2[j >> 1][j & 1] < p.thresh); };
 
+  // HANDOFF (the batched polynomial kernel; an unsegmented routed launch carries CompParams::walk): the forward of these views left
+  // this tile's walk summary (composite_common.hpp, kWalkWords) -- where its entry loop stopped, which entries reached a pixel, on
+  // which the threshold guard tripped.  They are this kernel's decisions too (the same bits in, the same operations), so the loop
+  // runs to `walked` without the per-entry vote on the pixels still alive and without the per-batch one, stages of the last batch
+  // only what was walked, passes an entry nobody sees on a scalar test and forms the guard's distances only where the guard
+  // tripped.  Entries behind the summary's kWalkK words are decided here as ever, under the same loop bound (the votes find
+  // nothing in front of it).  Two passes over one body: [e_lo, w_hi) on the summary -- empty without one --, [w_hi, e_end) without.
+  const uint32_t *const walk_rec = (HANDOFF && nseg <= 1 && p.walk != nullptr) ? p.walk + (size_t)tile * kWalkWords : nullptr;
+  const bool use_walk = walk_rec != nullptr;  // (uniform over the launch)
+  const int e_end = use_walk ? min((int)uniform_word(walk_rec), e_hi) : e_hi;
+  const int w_hi = use_walk ? min(e_end, kWalkK * KB) : e_lo;
+
   uint32_t exact_mask = 0u, tay_mask = 0u;
-  for (int base = e_lo; base < e_hi; base += KB) {
-    const int nb = min(KB, e_hi - base);
-    if (base > e_lo) __syncthreads();
-    stage_batch<MODE, CB, NT, KB, true, !POLY>(S, p, st + base, nb);
-    __syncthreads();
-    if constexpr (POLY) {
-      // (the forward's per-entry exact tier: the same splats, the same test -- a tile the forward gave up is not walked here)
-      exact_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)exact_tier_mask<NT>(p, S.id, nb, t, nullptr));
-      poly_transform<NT, KB>(p.col, S.id, Vs, Ws, nb, sm.tay_ok);
-      __syncthreads();
-      tay_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)(taylor_mask(sm.tay_ok, nb) & ~exact_mask));  // (as the forward)
-      taylor_convert<NT>(Ws, tay_mask, nb);
-      __syncthreads();
-    }
-
-    for (int g = 0; g < nb; ++g) {
-      bool any_alive = false;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
-      if (!wave_any(any_alive)) break;
-
-      // the record as plain scalars (a struct handed around by reference makes the compiler build the packed
-      // operands through scratch memory)
-      // (exact form: wave-uniform values moved to scalar registers -- nine vector registers less)
-      // (POLY: 108 registers leave room for the nine scalars as vector registers -- nine v_readfirstlane less per entry)
-      auto uni = [&](float v) { return !POLY ? wave_uniform(v) : v; };
-      const float r_mx = uni(S.mx[g]), r_my = uni(S.my[g]), r_a = uni(S.a[g]), r_c0 = uni(S.c0[g]), r_c1 = uni(S.c1[g]),
-                  r_c2 = uni(S.c2[g]), r_c3 = uni(S.c3[g]), r_p0 = uni(S.p0[g]), r_p1 = uni(S.p1[g]);
-      const float x = px - r_mx;
-      // G2 / ag2: the Gaussian and a G, ZEROED where the pixel does not take part (skip threshold, or not alive)
-      v2f y2[NP], G2[NP], ag2[NP], tx2[NP], ty2[NP];
-      bool any_con = false;
-      float guard_dist = 0.0f;
-#pragma unroll
-      for (int jp = 0; jp < NP; ++jp) {
-        y2[jp] = py2[jp] - splat2(r_my);
-        G2[jp] = gauss_sh_pair(r_c0, r_c1, r_c2, r_c3, r_p0, x, y2[jp], tx2[jp], ty2[jp]);
-        ag2[jp] = splat2(r_a) * G2[jp];
-        {
-          // the lane's smallest distance to the threshold (dead pixels included: a spurious trip re-tests per pixel)
-          const v2f dist = ag2[jp] - splat2(kMinAlpha);
-          const float dmin = fminf(fabsf(dist[0]), fabsf(dist[1]));
-          guard_dist = jp == 0 ? dmin : fminf(guard_dist, dmin);
-        }
+  // (always inlined: the running per-pixel state stays in registers)
+  auto walk_entries = [&](auto WALK_, const int lo, const int hi) __attribute__((always_inline)) {
+    constexpr bool WALK = decltype(WALK_)::value;  // this pass takes the forward's decisions
+    for (int base = lo; base < hi; base += KB) {
+      const int nb = min(KB, hi - base);
+      uint32_t walk_con = 0u, walk_guard = 0u;
+      if constexpr (WALK) {
+        walk_con = uniform_word(walk_rec + 1 + base / KB);
+        walk_guard = uniform_word(walk_rec + 1 + kWalkK + base / KB);
       }
-      const bool any_guard = guard_dist <= kMinAlpha * kGuardTol;
-      // within rounding of the skip threshold: the reference's arithmetic decides (as gauss_eval).  One wave-uniform
-      // test for all the lane's pixels: the branch is almost never taken (a handful of pixels per frame)
-      if (wave_any(any_guard)) {
+      (void)walk_con; (void)walk_guard;
+      if (base > e_lo) __syncthreads();
+      stage_batch<MODE, CB, NT, KB, true, !POLY>(S, p, st + base, nb);
+      __syncthreads();
+      if constexpr (POLY) {
+        // (the forward's per-entry exact tier: the same splats, the same test -- a tile the forward gave up is not walked here)
+        exact_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)exact_tier_mask<NT>(p, S.id, nb, t, nullptr));
+        poly_transform<NT, KB>(p.col, S.id, Vs, Ws, nb, sm.tay_ok);
+        __syncthreads();
+        tay_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)(taylor_mask(sm.tay_ok, nb) & ~exact_mask));  // (as the forward)
+        taylor_convert<NT>(Ws, tay_mask, nb);
+        __syncthreads();
+      }
+
+      for (int g = 0; g < nb; ++g) {
+        if constexpr (WALK) {
+          if (!((walk_con >> g) & 1u)) continue;  // the forward found nobody who sees this Gaussian
+        } else {
+          bool any_alive = false;
+#pragma unroll
+          for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
+          if (!wave_any(any_alive)) break;
+        }
+
+        // the record as plain scalars (a struct handed around by reference makes the compiler build the packed
+        // operands through scratch memory)
+        // (exact form: wave-uniform values moved to scalar registers -- nine vector registers less)
+        // (POLY: 108 registers leave room for the nine scalars as vector registers -- nine v_readfirstlane less per entry)
+        auto uni = [&](float v) { return !POLY ? wave_uniform(v) : v; };
+        const float r_mx = uni(S.mx[g]), r_my = uni(S.my[g]), r_a = uni(S.a[g]), r_c0 = uni(S.c0[g]), r_c1 = uni(S.c1[g]),
+                    r_c2 = uni(S.c2[g]), r_c3 = uni(S.c3[g]), r_p0 = uni(S.p0[g]), r_p1 = uni(S.p1[g]);
+        const float x = px - r_mx;
+        // G2 / ag2: the Gaussian and a G, ZEROED where the pixel does not take part (skip threshold, or not alive)
+        v2f y2[NP], G2[NP], ag2[NP], tx2[NP], ty2[NP], q2[NP];
+        bool any_con = false;
+#pragma unroll
+        for (int jp = 0; jp < NP; ++jp) {
+          y2[jp] = py2[jp] - splat2(r_my);
+          G2[jp] = gauss_sh_pair(r_c0, r_c1, r_c2, r_c3, r_p0, x, y2[jp], tx2[jp], ty2[jp], q2[jp]);
+          ag2[jp] = splat2(r_a) * G2[jp];
+        }
+        // within rounding of the skip threshold: the reference's arithmetic decides (as gauss_eval).  One wave-uniform
+        // test for all the lane's pixels: the branch is almost never taken (a handful of pixels per frame).  With the forward's
+        // summary the test is its bit: no distances are formed but the per-pixel ones behind a trip.
+        uint32_t guarded;
+        if constexpr (WALK) guarded = (walk_guard >> g) & 1u;
+        else guarded = sh_guard_trips<NP>(ag2, q2);
+        if (guarded != 0u) {
+#pragma unroll
+          for (int jp = 0; jp < NP; ++jp)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+              if (alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
+                G2[jp][e] = gauss_ref_f32(r_mx, r_my, r_c0, r_c1, r_c2, r_c3, px, py2[jp][e]);
+                ag2[jp][e] = r_a * G2[jp][e];
+              }
+        }
 #pragma unroll
         for (int jp = 0; jp < NP; ++jp)
 #pragma unroll
-          for (int e = 0; e < 2; ++e)
-            if (alive(2 * jp + e) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
-              G2[jp][e] = gauss_ref_f32(r_mx, r_my, r_c0, r_c1, r_c2, r_c3, px, py2[jp][e]);
-              ag2[jp][e] = r_a * G2[jp][e];
-            }
-      }
-#pragma unroll
-      for (int jp = 0; jp < NP; ++jp)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const bool con = alive(2 * jp + e) && !(ag2[jp][e] < kMinAlpha);
-          G2[jp][e] = con ? G2[jp][e] : 0.0f;
-          if constexpr (!POLY) ag2[jp][e] = con ? ag2[jp][e] : 0.0f;
-          any_con |= con;
-        }
-      if constexpr (POLY) {  // the same products again, from the masked G: two packed multiplies instead of four selects
-#pragma unroll
-        for (int jp = 0; jp < NP; ++jp) {
-          ag2[jp] = splat2(r_a) * G2[jp];
-        }
-      }
-      // (skipping a pixel PAIR none of whose 128 pixels takes part -- pair-major code, one wave-uniform test per pair -- was
-      // measured again in round 3 with the polynomial body: 4 488 vs 4 507 renders/s, profiles/r03_ab_pairskip_polyonly.txt)
-      if (!wave_any(any_con)) continue;  // nobody in the wave sees this Gaussian
-
-      constexpr int PCH = CCP <= 2 ? 2 : (CCP <= 4 ? 4 : (CCP <= 8 ? 8 : 16));  // one channel's components in its reduction
-      float chsum[3] = {0.0f, 0.0f, 0.0f};
-      const float *cg = POLY ? &Ws[g * 3 * kPolyStride] : &S.col[g * TR::NCOLP];
-      float rs[POLY ? 3 : 1][3];  // POLY: the channels' row sums (G0, G1, G2), reduced after the geometric part
-      v2f w2[NP], inv1m2[NP], pAG2[NP];
-#pragma unroll
-      for (int jp = 0; jp < NP; ++jp) {
-        w2[jp] = POLY ? Tr2[jp] * ag2[jp] : (splat2(r_a) * Tr2[jp]) * G2[jp];  // the forward's (a T) G -- POLY: T (a G) --, or 0
-        if constexpr (!POLY) {
-          const v2f om = one_minus2(ag2[jp]);
-          inv1m2[jp] = v2f{__builtin_amdgcn_rcpf(om[0]), __builtin_amdgcn_rcpf(om[1])};
-        }
-        pAG2[jp] = v2f{0.0f, 0.0f};
-      }
-      if constexpr (POLY) {
-        // colours as in the forward: the staged rows at the lane's pixels (or the exact tier's logits), colours already in the
-        // Taylor tier -- otherwise the three channels' denominators and ONE reciprocal per pixel for the three sigmoids and
-        // 1 / (1 - a G):  1 / x_i = (1 / prod x) * prod_{j != i} x_j  (|s| <= 40 by poly_transform, 1 - a G >= 0.01)
-        v2f yv[3][NP];
-        if ((exact_mask >> g) & 1u) exact_tier_logits_all<PPL>(p, __builtin_amdgcn_readfirstlane(S.id[g]), px, py2, yv);
-        else poly_rows_at_pixels<NP>(cg, pu2, pv2, yv);
-        v2f om2[NP];  // 1 - a G (>= 0.01)
-#pragma unroll
-        for (int jp = 0; jp < NP; ++jp) om2[jp] = one_minus2(ag2[jp]);
-        if ((tay_mask >> g) & 1u) {  // (wave-uniform; the ordinary case)
-#pragma unroll
-          for (int jp = 0; jp < NP; ++jp) inv1m2[jp] = v2f{__builtin_amdgcn_rcpf(om2[jp][0]), __builtin_amdgcn_rcpf(om2[jp][1])};
-        } else {
+          for (int e = 0; e < 2; ++e) {
+            // (radial < 0: gauss_eval's G = 0, which no pixel contributes with -- a term of the mask, see gauss_sh_pair)
+            const bool con = alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && !(ag2[jp][e] < kMinAlpha);
+            G2[jp][e] = con ? G2[jp][e] : 0.0f;
+            if constexpr (!POLY) ag2[jp][e] = con ? ag2[jp][e] : 0.0f;
+            any_con |= con;
+          }
+        if constexpr (POLY) {  // the same products again, from the masked G: two packed multiplies instead of four selects
 #pragma unroll
           for (int jp = 0; jp < NP; ++jp) {
-            v2f den[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) den[c] = splat2(1.0f) + v2f{__builtin_amdgcn_exp2f(yv[c][jp][0]), __builtin_amdgcn_exp2f(yv[c][jp][1])};
-            const v2f om = om2[jp];
-            const v2f d01 = den[0] * den[1], d2o = den[2] * om;
-            const v2f dd = d01 * d2o;
-            const v2f r = v2f{__builtin_amdgcn_rcpf(dd[0]), __builtin_amdgcn_rcpf(dd[1])};
-            const v2f r01 = r * d2o, r2o = r * d01;  // 1 / (d0 d1), 1 / (d2 (1 - a G))
-            yv[0][jp] = r01 * den[1];
-            yv[1][jp] = r01 * den[0];
-            yv[2][jp] = r2o * om;
-            inv1m2[jp] = r2o * den[2];
+            ag2[jp] = splat2(r_a) * G2[jp];
           }
         }
-        v2f gy2[NP];  // sum_c grad_out_c * colour_c
+        // (skipping a pixel PAIR none of whose 128 pixels takes part -- pair-major code, one wave-uniform test per pair -- was
+        // measured again in round 3 with the polynomial body: 4 488 vs 4 507 renders/s, profiles/r03_ab_pairskip_polyonly.txt)
+        // (with the summary's bit the entry was passed over at the top of the loop)
+        if constexpr (!WALK) {
+          if (!wave_any(any_con)) continue;  // nobody in the wave sees this Gaussian
+        }
+        (void)any_con;
+
+        constexpr int PCH = CCP <= 2 ? 2 : (CCP <= 4 ? 4 : (CCP <= 8 ? 8 : 16));  // one channel's components in its reduction
+        float chsum[3] = {0.0f, 0.0f, 0.0f};
+        const float *cg = POLY ? &Ws[g * 3 * kPolyStride] : &S.col[g * TR::NCOLP];
+        float rs[POLY ? 3 : 1][3];  // POLY: the channels' row sums (G0, G1, G2), reduced after the geometric part
+        v2f w2[NP], inv1m2[NP], pAG2[NP];
+#pragma unroll
+        for (int jp = 0; jp < NP; ++jp) {
+          w2[jp] = POLY ? Tr2[jp] * ag2[jp] : (splat2(r_a) * Tr2[jp]) * G2[jp];  // the forward's (a T) G -- POLY: T (a G) --, or 0
+          if constexpr (!POLY) {
+            const v2f om = one_minus2(ag2[jp]);
+            inv1m2[jp] = v2f{__builtin_amdgcn_rcpf(om[0]), __builtin_amdgcn_rcpf(om[1])};
+          }
+          pAG2[jp] = v2f{0.0f, 0.0f};
+        }
+        if constexpr (POLY) {
+          // colours as in the forward: the staged rows at the lane's pixels (or the exact tier's logits), colours already in the
+          // Taylor tier -- otherwise the three channels' denominators and ONE reciprocal per pixel for the three sigmoids and
+          // 1 / (1 - a G):  1 / x_i = (1 / prod x) * prod_{j != i} x_j  (|s| <= 40 by poly_transform, 1 - a G >= 0.01)
+          v2f yv[3][NP];
+          if ((exact_mask >> g) & 1u) exact_tier_logits_all<PPL>(p, __builtin_amdgcn_readfirstlane(S.id[g]), px, py2, yv);
+          else poly_rows_at_pixels<NP>(cg, pu2, pv2, yv);
+          v2f om2[NP];  // 1 - a G (>= 0.01)
+#pragma unroll
+          for (int jp = 0; jp < NP; ++jp) om2[jp] = one_minus2(ag2[jp]);
+          if ((tay_mask >> g) & 1u) {  // (wave-uniform; the ordinary case)
+#pragma unroll
+            for (int jp = 0; jp < NP; ++jp) inv1m2[jp] = v2f{__builtin_amdgcn_rcpf(om2[jp][0]), __builtin_amdgcn_rcpf(om2[jp][1])};
+          } else {
+#pragma unroll
+            for (int jp = 0; jp < NP; ++jp) {
+              v2f den[3];
+#pragma unroll
+              for (int c = 0; c < 3; ++c) den[c] = splat2(1.0f) + v2f{__builtin_amdgcn_exp2f(yv[c][jp][0]), __builtin_amdgcn_exp2f(yv[c][jp][1])};
+              const v2f om = om2[jp];
+              const v2f d01 = den[0] * den[1], d2o = den[2] * om;
+              const v2f dd = d01 * d2o;
+              const v2f r = v2f{__builtin_amdgcn_rcpf(dd[0]), __builtin_amdgcn_rcpf(dd[1])};
+              const v2f r01 = r * d2o, r2o = r * d01;  // 1 / (d0 d1), 1 / (d2 (1 - a G))
+              yv[0][jp] = r01 * den[1];
+              yv[1][jp] = r01 * den[0];
+              yv[2][jp] = r2o * om;
+              inv1m2[jp] = r2o * den[2];
+            }
+          }
+          v2f gy2[NP];  // sum_c grad_out_c * colour_c
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            // d L / d w[c][r] = sum over pixels of gs * monomial_r: the lane's sums of gs, gs v, gs v^2, then its column's u
+            v2f g0, g1, g2;
+#pragma unroll
+            for (int jp = 0; jp < NP; ++jp) {
+              const v2f y_ = yv[c][jp];
+              const v2f dy = fma2(-y_, y_, y_);  // y (1 - y)
+              const v2f go = go2[jp][c];  // (registers: this body has them to spare; the exact one reads its copy in LDS)
+              const v2f gs = (w2[jp] * dy) * go;
+              gy2[jp] = c == 0 ? go * y_ : fma2(go, y_, gy2[jp]);
+              if (jp == 0) { g0 = gs; g1 = gs * pv2[jp]; g2 = gs * pvsq2[jp]; }
+              else { g0 = g0 + gs; g1 = fma2(gs, pv2[jp], g1); g2 = fma2(gs, pvsq2[jp], g2); }
+            }
+            // (the column's u multiplies them behind the cross-row levels of the reduction: wave_reduce_scatter_sep16)
+            rs[c][0] = add_scalar(g0[0], g0[1]); rs[c][1] = add_scalar(g1[0], g1[1]); rs[c][2] = add_scalar(g2[0], g2[1]);
+          }
+#pragma unroll
+          for (int jp = 0; jp < NP; ++jp) {
+            R2[jp] = fma2(-w2[jp], gy2[jp], R2[jp]);  // the suffix behind this splat (vol_render_sh.h:328-333), grad_out-weighted
+            pAG2[jp] = fma2(gy2[jp], Tr2[jp], -(R2[jp] * inv1m2[jp]));
+          }
+        }
+        v2f gyx2[NP];
+        if constexpr (!POLY) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          // d L / d w[c][r] = sum over pixels of gs * monomial_r: the lane's sums of gs, gs v, gs v^2, then its column's u
-          v2f g0, g1, g2;
+          v2f q[NPAIR], gq[NPAIR];
 #pragma unroll
-          for (int jp = 0; jp < NP; ++jp) {
-            const v2f y_ = yv[c][jp];
-            const v2f dy = fma2(-y_, y_, y_);  // y (1 - y)
-            const v2f go = go2[jp][c];  // (registers: this body has them to spare; the exact one reads its copy in LDS)
+          for (int k = 0; k < NPAIR; ++k) q[k] = *reinterpret_cast<const v2f *>(cg + c * CCP + 2 * k);
+          // one pixel pair: colours, suffix, d/d(a G), and its share of d/d(sh) (FIRST: it initialises the accumulators)
+          auto pair_colour = [&](auto JP, auto FIRST) {
+            constexpr int jp = decltype(JP)::value;
+            constexpr bool first = decltype(FIRST)::value;
+            // -log2(e) * (sh . Y) of the pair's two pixels: the two dot products interleaved (a v_pk_fma that depends
+            // on the previous instruction costs a wait state)
+            v2f sa = q[0] * Yp[2 * jp][0], sb = q[0] * Yp[2 * jp + 1][0];
+#pragma unroll
+            for (int k = 1; k < NPAIR; ++k) {
+              sa = fma2(q[k], Yp[2 * jp][k], sa);
+              sb = fma2(q[k], Yp[2 * jp + 1][k], sb);
+            }
+            const v2f sp = v2f{add_scalar(sa[0], sa[1]), add_scalar(sb[0], sb[1])};
+            const v2f den = splat2(1.0f) + v2f{__builtin_amdgcn_exp2f(sp[0]), __builtin_amdgcn_exp2f(sp[1])};
+            const v2f yv = v2f{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+            const v2f dy = fma2(-yv, yv, yv);  // y (1 - y)
+            const v2f go = go_s[(c * NP + jp) * NT + t];
             const v2f gs = (w2[jp] * dy) * go;
-            gy2[jp] = c == 0 ? go * y_ : fma2(go, y_, gy2[jp]);
-            if (jp == 0) { g0 = gs; g1 = gs * pv2[jp]; g2 = gs * pvsq2[jp]; }
-            else { g0 = g0 + gs; g1 = fma2(gs, pv2[jp], g1); g2 = fma2(gs, pvsq2[jp], g2); }
+            gyx2[jp] = c == 0 ? go * yv : fma2(go, yv, gyx2[jp]);  // sum_c grad_out_c * colour_c (see R2)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const v2f gse = splat2(gs[e]);
+              if (first && e == 0) {
+#pragma unroll
+                for (int k = 0; k < NPAIR; ++k) gq[k] = gse * Yp[2 * jp + e][k];
+              } else {
+#pragma unroll
+                for (int k = 0; k < NPAIR; ++k) gq[k] = fma2(gse, Yp[2 * jp + e][k], gq[k]);
+              }
+            }
+          };
+          // (skipping a pair none of whose pixels contributes -- a wave-uniform branch per pair and channel, ~1 pair in 5
+          // on the headline workload -- was measured: -1.5 % on a lone launch, +1 % with two batches in flight, 32 more
+          // registers; not kept)
+          pair_colour(std::integral_constant<int, 0>{}, std::true_type{});
+          if constexpr (NP > 1) pair_colour(std::integral_constant<int, NP - 1>{}, std::false_type{});
+          {
+            v2f t[PCH / 2];
+#pragma unroll
+            for (int k = 0; k < PCH / 2; ++k) t[k] = k < NPAIR ? gq[k < NPAIR ? k : 0] : v2f{0.0f, 0.0f};
+            chsum[c] = wave_reduce_scatter2_rows<PCH>(t);
           }
-          // (the column's u multiplies them behind the cross-row levels of the reduction: wave_reduce_scatter_sep16)
-          rs[c][0] = add_scalar(g0[0], g0[1]); rs[c][1] = add_scalar(g1[0], g1[1]); rs[c][2] = add_scalar(g2[0], g2[1]);
         }
+#pragma unroll
+        for (int jp = 0; jp < NP; ++jp) {  // the grad_out-weighted suffix behind this splat, and d L / d (a G) from it (as POLY)
+          R2[jp] = fma2(-w2[jp], gyx2[jp], R2[jp]);
+          pAG2[jp] = fma2(gyx2[jp], Tr2[jp], -(R2[jp] * inv1m2[jp]));
+        }
+        }  // !POLY
+        // mean2d (2) | cov2d (4) | alpha (1): kernel_gaussian_2d_backward (kernels.h:394-418), packed over the pair
+        // and summed over the lane's pairs; the two halves are added at the end
+        const float inv_det = r_p1;
+        v2f gm0 = {0.f, 0.f}, gm1 = gm0, gc0 = gm0, gc1 = gm0, gc3 = gm0, gal = gm0;
 #pragma unroll
         for (int jp = 0; jp < NP; ++jp) {
-          R2[jp] = fma2(-w2[jp], gy2[jp], R2[jp]);  // the suffix behind this splat (vol_render_sh.h:328-333), grad_out-weighted
-          pAG2[jp] = fma2(gy2[jp], Tr2[jp], -(R2[jp] * inv1m2[jp]));
-        }
-      }
-      v2f gyx2[NP];
-      if constexpr (!POLY) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v2f q[NPAIR], gq[NPAIR];
-#pragma unroll
-        for (int k = 0; k < NPAIR; ++k) q[k] = *reinterpret_cast<const v2f *>(cg + c * CCP + 2 * k);
-        // one pixel pair: colours, suffix, d/d(a G), and its share of d/d(sh) (FIRST: it initialises the accumulators)
-        auto pair_colour = [&](auto JP, auto FIRST) {
-          constexpr int jp = decltype(JP)::value;
-          constexpr bool first = decltype(FIRST)::value;
-          // -log2(e) * (sh . Y) of the pair's two pixels: the two dot products interleaved (a v_pk_fma that depends
-          // on the previous instruction costs a wait state)
-          v2f sa = q[0] * Yp[2 * jp][0], sb = q[0] * Yp[2 * jp + 1][0];
-#pragma unroll
-          for (int k = 1; k < NPAIR; ++k) {
-            sa = fma2(q[k], Yp[2 * jp][k], sa);
-            sb = fma2(q[k], Yp[2 * jp + 1][k], sb);
+          const v2f pa = pAG2[jp];  // (its uses below are products with the masked G / a G)
+          const v2f gg = pa * ag2[jp];
+          if constexpr (MOM) {  // (gm0, gm1 | gc0, gc1, gc3) hold the moments (Mx, My | Mxx, Mxy, Myy)
+            const v2f t_ = gg * tx2[jp], s_ = gg * ty2[jp];
+            gm0 = jp == 0 ? t_ : gm0 + t_;
+            gm1 = jp == 0 ? s_ : gm1 + s_;
+            gc0 = jp == 0 ? t_ * tx2[jp] : fma2(t_, tx2[jp], gc0);
+            gc1 = jp == 0 ? t_ * ty2[jp] : fma2(t_, ty2[jp], gc1);
+            gc3 = jp == 0 ? s_ * ty2[jp] : fma2(s_, ty2[jp], gc3);
+          } else {
+            const v2f vx = (splat2(x * r_c3) - y2[jp] * splat2(r_c2)) * splat2(inv_det);
+            const v2f vy = (y2[jp] * splat2(r_c0) - splat2(x * r_c1)) * splat2(inv_det);
+            gm0 = fma2(gg, vx, gm0);
+            gm1 = fma2(gg, vy, gm1);
+            const v2f h = splat2(0.5f) * gg;
+            const v2f hvx = h * vx;
+            gc0 = fma2(hvx, vx, gc0);
+            gc1 = fma2(hvx, vy, gc1);
+            gc3 = fma2(h * vy, vy, gc3);
           }
-          const v2f sp = v2f{add_scalar(sa[0], sa[1]), add_scalar(sb[0], sb[1])};
-          const v2f den = splat2(1.0f) + v2f{__builtin_amdgcn_exp2f(sp[0]), __builtin_amdgcn_exp2f(sp[1])};
-          const v2f yv = v2f{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-          const v2f dy = fma2(-yv, yv, yv);  // y (1 - y)
-          const v2f go = go_s[(c * NP + jp) * NT + t];
-          const v2f gs = (w2[jp] * dy) * go;
-          gyx2[jp] = c == 0 ? go * yv : fma2(go, yv, gyx2[jp]);  // sum_c grad_out_c * colour_c (see R2)
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const v2f gse = splat2(gs[e]);
-            if (first && e == 0) {
-#pragma unroll
-              for (int k = 0; k < NPAIR; ++k) gq[k] = gse * Yp[2 * jp + e][k];
-            } else {
-#pragma unroll
-              for (int k = 0; k < NPAIR; ++k) gq[k] = fma2(gse, Yp[2 * jp + e][k], gq[k]);
-            }
-          }
-        };
-        // (skipping a pair none of whose pixels contributes -- a wave-uniform branch per pair and channel, ~1 pair in 5
-        // on the headline workload -- was measured: -1.5 % on a lone launch, +1 % with two batches in flight, 32 more
-        // registers; not kept)
-        pair_colour(std::integral_constant<int, 0>{}, std::true_type{});
-        if constexpr (NP > 1) pair_colour(std::integral_constant<int, NP - 1>{}, std::false_type{});
-        {
-          v2f t[PCH / 2];
-#pragma unroll
-          for (int k = 0; k < PCH / 2; ++k) t[k] = k < NPAIR ? gq[k < NPAIR ? k : 0] : v2f{0.0f, 0.0f};
-          chsum[c] = wave_reduce_scatter2_rows<PCH>(t);
+          gal = fma2(pa, G2[jp], gal);
+          Tr2[jp] = Tr2[jp] * one_minus2(ag2[jp]);  // T (1 - a G) if it contributed (explicit: as the forward)
         }
-      }
+        const float m0 = gm0[0] + gm0[1], m1 = gm1[0] + gm1[1];
+        const float c0 = gc0[0] + gc0[1], c1 = gc1[0] + gc1[1], c3 = gc3[0] + gc3[1];
+        const float ga = gal[0] + gal[1];
+        if constexpr (POLY) {
+          // Rows before columns (wave_reduce_scatter_sep16): the lanes at distances 32 and 16 share their column, so the channels' row
+          // sums and the six DISTINCT geometric components (grad_cov[1] and grad_cov[2] receive the same value, kernels.h:414-415)
+          // cross the rows as 15 values -- class c = channel c's (G0, G1, G2) + one geometric value, class 3 the other three -- and
+          // the column's u enters once, on the row sums: slots (1, v, u, v^2, uv, u^2 | geometric) per channel.
+          v2f t8[8] = {v2f{rs[0][0], rs[0][1]}, v2f{rs[0][2], m0}, v2f{rs[1][0], rs[1][1]}, v2f{rs[1][2], c0},
+                       v2f{rs[2][0], rs[2][1]}, v2f{rs[2][2], c3}, v2f{m1, c1}, v2f{ga, 0.0f}};
+          const float tot = wave_reduce_scatter_sep16(t8, pu);
+          const int comp = sep16_comp(lane);  // 8 * (channel, or 3 for the geometric class) + slot
+          const size_t id = (size_t)S.id[g];
+          // d L / d sh[c][k] = sum_r gw[c][r] V[r][k]: the 18 reduced values go through LDS, lanes (c, k) = (lane / 16,
+          // lane % 16) expand them with their column of V (one wavefront per workgroup: the barrier is a wait)
+          if (sep16_owner(lane) && comp < 3 * 8 && (comp & 7) < kPolyNB) gw_s[comp] = tot;
+          // the geometric components, ONE atomic instruction (geo_base / geo_stride: the lane's slot, fixed before the loop)
+          if (geo_base != nullptr) atomicAdd(geo_base + id * geo_stride, tot);
+          __syncthreads();
+          if (lane < 48) {
+            const float *gw = &gw_s[(lane >> 4) * 8];
+            const float *vk = &Vs[lane & 15];  // column (lane & 15) of V, from LDS as the sums are: six registers less across the loop
+            float acc = gw[0] * vk[0];
 #pragma unroll
-      for (int jp = 0; jp < NP; ++jp) {  // the grad_out-weighted suffix behind this splat, and d L / d (a G) from it (as POLY)
-        R2[jp] = fma2(-w2[jp], gyx2[jp], R2[jp]);
-        pAG2[jp] = fma2(gyx2[jp], Tr2[jp], -(R2[jp] * inv1m2[jp]));
-      }
-      }  // !POLY
-      // mean2d (2) | cov2d (4) | alpha (1): kernel_gaussian_2d_backward (kernels.h:394-418), packed over the pair
-      // and summed over the lane's pairs; the two halves are added at the end
-      const float inv_det = r_p1;
-      v2f gm0 = {0.f, 0.f}, gm1 = gm0, gc0 = gm0, gc1 = gm0, gc3 = gm0, gal = gm0;
-#pragma unroll
-      for (int jp = 0; jp < NP; ++jp) {
-        const v2f pa = pAG2[jp];  // (its uses below are products with the masked G / a G)
-        const v2f gg = pa * ag2[jp];
-        if constexpr (MOM) {  // (gm0, gm1 | gc0, gc1, gc3) hold the moments (Mx, My | Mxx, Mxy, Myy)
-          const v2f t_ = gg * tx2[jp], s_ = gg * ty2[jp];
-          gm0 = jp == 0 ? t_ : gm0 + t_;
-          gm1 = jp == 0 ? s_ : gm1 + s_;
-          gc0 = jp == 0 ? t_ * tx2[jp] : fma2(t_, tx2[jp], gc0);
-          gc1 = jp == 0 ? t_ * ty2[jp] : fma2(t_, ty2[jp], gc1);
-          gc3 = jp == 0 ? s_ * ty2[jp] : fma2(s_, ty2[jp], gc3);
+            for (int r = 1; r < kPolyNB; ++r) acc = fmaf(gw[r], vk[r * 16], acc);
+            atomicAdd(p.g_col + (size_t)TR::NCOL * id + lane, acc);  // (c, k) -> 16 c + k = lane
+          }
+          __syncthreads();  // gw_s is consumed before the next splat overwrites it
         } else {
-          const v2f vx = (splat2(x * r_c3) - y2[jp] * splat2(r_c2)) * splat2(inv_det);
-          const v2f vy = (y2[jp] * splat2(r_c0) - splat2(x * r_c1)) * splat2(inv_det);
-          gm0 = fma2(gg, vx, gm0);
-          gm1 = fma2(gg, vy, gm1);
-          const v2f h = splat2(0.5f) * gg;
-          const v2f hvx = h * vx;
-          gc0 = fma2(hvx, vx, gc0);
-          gc1 = fma2(hvx, vy, gc1);
-          gc3 = fma2(h * vy, vy, gc3);
+          // grad_cov[1] and grad_cov[2] receive the same value (kernels.h:414-415)
+          // (MOM: (Mx, My) (Mxx, Mxy) (Myy, alpha) -> mean[0..1], cov[0..1], cov[2], alpha)
+          v2f ex[4] = {v2f{m0, m1}, v2f{c0, c1}, MOM ? v2f{c3, ga} : v2f{c1, c3}, MOM ? v2f{0.0f, 0.0f} : v2f{ga, 0.0f}};
+          const float exsum = wave_reduce_scatter2_rows<8>(ex);
+          const float tot = quad_reduce_scatter4(chsum[0], chsum[1], chsum[2], exsum);
+          const int m = lane & 3;  // the vector this lane ends up with: channel 0 / 1 / 2 / geometric
+          const size_t id = (size_t)S.id[g];
+          float *dst = nullptr;
+          if (m < 3) {
+            const int k = scatter_comp<PCH>(lane);
+            if (scatter_rows_owner<PCH>(lane) && k < TR::CC) dst = p.g_col + (size_t)TR::NCOL * id + m * TR::CC + k;
+          } else if (m == 3 && scatter_rows_owner<8>(lane)) {
+            const int e = scatter_comp<8>(lane);
+            if (e < 2) dst = p.g_mean + 2 * id + e;
+            else if (e < (MOM ? 5 : 6)) dst = p.g_cov + 4 * id + (e - 2);
+            else if (e == (MOM ? 5 : 6)) dst = p.g_alpha + id;
+          }
+          if (dst != nullptr) atomicAdd(dst, tot);
         }
-        gal = fma2(pa, G2[jp], gal);
-        Tr2[jp] = Tr2[jp] * one_minus2(ag2[jp]);  // T (1 - a G) if it contributed (explicit: as the forward)
       }
-      const float m0 = gm0[0] + gm0[1], m1 = gm1[0] + gm1[1];
-      const float c0 = gc0[0] + gc0[1], c1 = gc1[0] + gc1[1], c3 = gc3[0] + gc3[1];
-      const float ga = gal[0] + gal[1];
-      if constexpr (POLY) {
-        // Rows before columns (wave_reduce_scatter_sep16): the lanes at distances 32 and 16 share their column, so the channels' row
-        // sums and the six DISTINCT geometric components (grad_cov[1] and grad_cov[2] receive the same value, kernels.h:414-415)
-        // cross the rows as 15 values -- class c = channel c's (G0, G1, G2) + one geometric value, class 3 the other three -- and
-        // the column's u enters once, on the row sums: slots (1, v, u, v^2, uv, u^2 | geometric) per channel.
-        v2f t8[8] = {v2f{rs[0][0], rs[0][1]}, v2f{rs[0][2], m0}, v2f{rs[1][0], rs[1][1]}, v2f{rs[1][2], c0},
-                     v2f{rs[2][0], rs[2][1]}, v2f{rs[2][2], c3}, v2f{m1, c1}, v2f{ga, 0.0f}};
-        const float tot = wave_reduce_scatter_sep16(t8, pu);
-        const int comp = sep16_comp(lane);  // 8 * (channel, or 3 for the geometric class) + slot
-        const size_t id = (size_t)S.id[g];
-        // d L / d sh[c][k] = sum_r gw[c][r] V[r][k]: the 18 reduced values go through LDS, lanes (c, k) = (lane / 16,
-        // lane % 16) expand them with their column of V (one wavefront per workgroup: the barrier is a wait)
-        if (sep16_owner(lane) && comp < 3 * 8 && (comp & 7) < kPolyNB) gw_s[comp] = tot;
-        // the geometric components, ONE atomic instruction (geo_base / geo_stride: the lane's slot, fixed before the loop)
-        if (geo_base != nullptr) atomicAdd(geo_base + id * geo_stride, tot);
-        __syncthreads();
-        if (lane < 48) {
-          const float *gw = &gw_s[(lane >> 4) * 8];
-          const float *vk = &Vs[lane & 15];  // column (lane & 15) of V, from LDS as the sums are: six registers less across the loop
-          float acc = gw[0] * vk[0];
+      if constexpr (!WALK) {  // (a pass on the summary ends where the forward stopped: no vote)
+        bool any_alive = false;
 #pragma unroll
-          for (int r = 1; r < kPolyNB; ++r) acc = fmaf(gw[r], vk[r * 16], acc);
-          atomicAdd(p.g_col + (size_t)TR::NCOL * id + lane, acc);  // (c, k) -> 16 c + k = lane
-        }
-        __syncthreads();  // gw_s is consumed before the next splat overwrites it
-      } else {
-        // grad_cov[1] and grad_cov[2] receive the same value (kernels.h:414-415)
-        // (MOM: (Mx, My) (Mxx, Mxy) (Myy, alpha) -> mean[0..1], cov[0..1], cov[2], alpha)
-        v2f ex[4] = {v2f{m0, m1}, v2f{c0, c1}, MOM ? v2f{c3, ga} : v2f{c1, c3}, MOM ? v2f{0.0f, 0.0f} : v2f{ga, 0.0f}};
-        const float exsum = wave_reduce_scatter2_rows<8>(ex);
-        const float tot = quad_reduce_scatter4(chsum[0], chsum[1], chsum[2], exsum);
-        const int m = lane & 3;  // the vector this lane ends up with: channel 0 / 1 / 2 / geometric
-        const size_t id = (size_t)S.id[g];
-        float *dst = nullptr;
-        if (m < 3) {
-          const int k = scatter_comp<PCH>(lane);
-          if (scatter_rows_owner<PCH>(lane) && k < TR::CC) dst = p.g_col + (size_t)TR::NCOL * id + m * TR::CC + k;
-        } else if (m == 3 && scatter_rows_owner<8>(lane)) {
-          const int e = scatter_comp<8>(lane);
-          if (e < 2) dst = p.g_mean + 2 * id + e;
-          else if (e < (MOM ? 5 : 6)) dst = p.g_cov + 4 * id + (e - 2);
-          else if (e == (MOM ? 5 : 6)) dst = p.g_alpha + id;
-        }
-        if (dst != nullptr) atomicAdd(dst, tot);
+        for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
+        if (__syncthreads_or((int)any_alive) == 0) break;
       }
     }
-    bool any_alive = false;
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
-    if (__syncthreads_or((int)any_alive) == 0) break;
-  }
+  };
+  if constexpr (HANDOFF) walk_entries(std::true_type{}, e_lo, w_hi);
+  walk_entries(std::false_type{}, w_hi, e_end);
 }
 // (the persistent fallback runs at 152 registers, the exact kernel at 148: three wavefronts per SIMD.  It only renders views whose
 // coefficient bound fails while a batch mate's holds.)
@@ -1809,7 +1885,7 @@ k_composite_bwd_sh_vec(CompParams p_arg, ViewPack<BATCH> pack) {
     if (pp->sh_rows == nullptr && !view_ok) return;  // per-view routing: this view is the exact fallback's
     CompParams p = view_params<PSD>(*pp, ps);
     if (view_ok) p.sh_rows = nullptr;  // (as the forward: the same device value, the same decision)
-    composite_bwd_sh_vec_tile<4, 4, kPolyNB, false, MOM>(p, bid, grid, sm);
+    composite_bwd_sh_vec_tile<4, 4, kPolyNB, false, MOM, true>(p, bid, grid, sm);
   } else {
     const CompParams *pp = BATCH ? &plist[batch_view(p_arg, bid, &grid)] : &p_arg;  // see k_composite_fwd
     const CompParams p = view_params<PSD>(*pp, view_pixel_sizes<PSD>(*pp));
@@ -2928,9 +3004,24 @@ static bool batch_can_be_polynomial(const std::vector<CompParams> &ps) {
 }
 
 size_t gsgen_sh_batch_workspace_bytes(uint32_t n_views) { return 2 * (size_t)n_views * sizeof(CompParams); }
-// ... + one flag byte per (view, tile) for the per-tile routing of the *_routed entry points
+// ... + one flag byte per (view, tile) for the per-tile routing of the *_routed entry points (padded to 16 bytes) + the walk
+// summary, kWalkWords uint32 per (view, tile) (composite_common.hpp)
+static size_t sh_batch_flag_bytes(uint32_t n_views, uint32_t n_tiles) { return ((size_t)n_views * n_tiles + 15u) & ~(size_t)15u; }
 size_t gsgen_sh_batch_workspace_bytes_routed(uint32_t n_views, uint32_t n_tiles) {
-  return gsgen_sh_batch_workspace_bytes(n_views) + (((size_t)n_views * n_tiles + 15u) & ~(size_t)15u);
+  return gsgen_sh_batch_workspace_bytes(n_views) + sh_batch_flag_bytes(n_views, n_tiles) +
+         (size_t)n_views * n_tiles * kWalkWords * sizeof(uint32_t);
+}
+// The views' walk summaries inside a routed batch's workspace, for the launches that keep one: per-tile routing on per-splat
+// bounds (whose callers size the workspace with the function above), the polynomial kernels in play, no segments.  Forward and
+// backward of a batch apply the same rule to the same arguments.
+static void set_walk_summaries(std::vector<CompParams> &ps, void *batch_workspace, uint32_t n_tiles, bool bounded) {
+  const uint32_t B = (uint32_t)ps.size();
+  uint32_t *walk = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(batch_workspace) + gsgen_sh_batch_workspace_bytes(B) +
+                                                sh_batch_flag_bytes(B, n_tiles));
+  for (uint32_t b = 0; b < B; ++b) {
+    CompParams &p = ps[b];
+    p.walk = (bounded && p.tile_flags != nullptr && p.nseg <= 1) ? walk + (size_t)b * n_tiles * kWalkWords : nullptr;
+  }
 }
 
 int gsgen_vol_render_sh_batch(uint32_t n_views, const gsgen_sh_view *views, uint32_t N,
@@ -2971,6 +3062,7 @@ int gsgen_vol_render_sh_batch_routed(uint32_t n_views, const gsgen_sh_view *view
   const bool bounded = C == 4 && (sh_l1_bound != nullptr || sh_row_bounds != nullptr) && batch_can_be_polynomial(ps);
   if (!bounded)
     for (CompParams &p : ps) { p.sh_bound = nullptr; p.sh_rows = nullptr; p.tile_flags = nullptr; }
+  set_walk_summaries(ps, batch_workspace, n_tiles_h * n_tiles_w, bounded);
   hipStream_t s = (hipStream_t)stream;
   return launch_fwd_sh_batch((int)C, ps.data(), n_views, s, bounded);
 }
@@ -3016,6 +3108,7 @@ static int backward_sh_batch_routed(bool moments, uint32_t n_views, const gsgen_
   const bool bounded = C == 4 && (sh_l1_bound != nullptr || sh_row_bounds != nullptr) && batch_can_be_polynomial(ps);
   if (!bounded)
     for (CompParams &p : ps) { p.sh_bound = nullptr; p.sh_rows = nullptr; p.tile_flags = nullptr; }
+  set_walk_summaries(ps, batch_workspace, n_tiles_h * n_tiles_w, bounded);
   hipStream_t s = (hipStream_t)stream;
   return launch_bwd_sh_batch((int)C, ps.data(), n_views, s, bounded, moments);
 }

@@ -72,6 +72,9 @@ struct CompParams {
   // the top of the kernel in place of the two floats above, so that a captured step replays for other intrinsics (RGB / RGB + heads:
   // view_params below, a run-time test; SH: the <..., PSD = true> instantiations of k_composite_*_sh_vec, composite.hip)
   const float *ps_dev;
+  // SH degree 3, unsegmented routed batches: the view's walk summary, kWalkWords uint32 per tile (below) -- written by the batched
+  // polynomial forward, read by the batched polynomial backward.  NULL: every kernel decides for itself.
+  uint32_t *walk;
 };
 // a batched channel-mode kernel's parameter block: the view's entry of the kernel-argument table, pixel sizes from device memory if given
 __device__ __forceinline__ CompParams view_params(const CompParams &src) {
@@ -332,24 +335,84 @@ __device__ __forceinline__ float gauss_eval(const GRec &r, float x, float y, flo
 // gauss_eval<MODE_SH> element for element (v_pk_mul / v_pk_fma round exactly like their scalar forms), without the
 // threshold guard -- the caller applies it per pixel with gauss_ref_f32 as gauss_eval does.
 // tx, ty: det * Sigma^-1 d, the offsets the value is formed from (the moment form of the backward sums against them).
-__device__ __forceinline__ v2f gauss_sh_pair(float c0, float c1, float c2, float c3, float p0, float x, v2f y2, v2f &tx, v2f &ty) {
+// q2: the radial numerator.  The value returned is the RAW exponential: where q2 < 0 (a covariance that is not positive
+// semi-definite) gauss_eval delivers 0 (kernels.h:186-188), which here is the CALLER's to apply -- as one more term of the
+// contribution mask that zeroes G anyway (sh_pixel_contributes), compares and scalar mask operations instead of two selects per
+// pair; the raw value of such a pixel (>= 1, possibly inf, NaN once multiplied by a = 0) must reach nothing else: the
+// threshold guard leaves it out (sh_guard_trips).
+__device__ __forceinline__ v2f gauss_sh_pair(float c0, float c1, float c2, float c3, float p0, float x, v2f y2, v2f &tx, v2f &ty,
+                                             v2f &q2) {
 #pragma clang fp contract(off)
   const float xc1 = x * c1;
   const v2f yc2 = y2 * splat2(c2);
   tx = ffma2(splat2(x), splat2(c3), -yc2);
   ty = ffma2(y2, splat2(c0), -splat2(xc1));
   const v2f tyy = ty * y2;
-  const v2f q2 = ffma2(tx, splat2(x), tyy);
+  q2 = ffma2(tx, splat2(x), tyy);
   const v2f e = splat2(p0) * q2;
-  v2f G = {__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])};
-  G[0] = (q2[0] < 0.0f) ? 0.0f : G[0];
-  G[1] = (q2[1] < 0.0f) ? 0.0f : G[1];
-  return G;
+  return v2f{__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])};
 }
-__device__ __forceinline__ v2f gauss_sh_pair(float c0, float c1, float c2, float c3, float p0, float x, v2f y2) {
+__device__ __forceinline__ v2f gauss_sh_pair(float c0, float c1, float c2, float c3, float p0, float x, v2f y2, v2f &q2) {
   v2f tx, ty;
-  return gauss_sh_pair(c0, c1, c2, c3, p0, x, y2, tx, ty);
+  return gauss_sh_pair(c0, c1, c2, c3, p0, x, y2, tx, ty, q2);
 }
+// wave_any as a 0 / 1 WORD in a scalar register (a population count and a minimum, the latter spelled out: the compiler turns the
+// C form back into a bool, and a bool that crosses a branch is widened by a vector select and ORed into vector accumulators): the
+// bits of the walk summary are shifted and ORed together on the scalar unit.  (Seen with the clang 22.0.0git of ROCm 7.2; the asm can
+// go once `min(popcount(ballot), 1)` stays an integer through instruction selection.)
+__device__ __forceinline__ uint32_t wave_any_word(bool pred) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(pred));
+  uint32_t r;
+  asm("s_min_u32 %0, %1, 1" : "=s"(r) : "s"(c) : "scc");
+  return r;
+#else
+  return __ballot((int)pred) != 0ull ? 1u : 0u;
+#endif
+}
+// Does the threshold guard trip for this entry (wave-uniform, 0 / 1)?  ag2: a * (raw G) of the lane's pixel pairs, q2: their radial
+// numerators.  The answer is that of the per-pixel rule "a pixel with q >= 0 lies within kGuardTol of the skip threshold" (dead
+// pixels included: a spurious trip re-tests per pixel) -- with G zeroed where q < 0, as gauss_eval has it, such a pixel sits a whole
+// 1/255 from the threshold and never trips.  The ordinary entry pays the lane's smallest distance over ALL its pixels and one
+// compare; only when a lane that is near also holds a pixel with q < 0 (both rare, together a curiosity) are the pixels tested one
+// by one.  (A NaN distance drops out of fminf and fails the compare, before as now.)
+template <int NP>
+__device__ __forceinline__ uint32_t sh_guard_trips(const v2f (&ag2)[NP], const v2f (&q2)[NP]) {
+  float guard_dist = 0.0f;
+  bool lane_neg = false;
+#pragma unroll
+  for (int jp = 0; jp < NP; ++jp) {
+    const v2f dist = ag2[jp] - splat2(kMinAlpha);
+    const float dmin = fminf(fabsf(dist[0]), fabsf(dist[1]));
+    guard_dist = jp == 0 ? dmin : fminf(guard_dist, dmin);
+    lane_neg |= (q2[jp][0] < 0.0f) | (q2[jp][1] < 0.0f);
+  }
+  const bool near = guard_dist <= kMinAlpha * kGuardTol;
+  if (!wave_any(near)) return 0u;
+  if (!wave_any(near && lane_neg)) return 1u;  // the near lanes hold no such pixel: their distances are the masked ones
+  bool near_px = false;
+#pragma unroll
+  for (int jp = 0; jp < NP; ++jp)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) near_px |= !(q2[jp][e] < 0.0f) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol;
+  return wave_any_word(near_px);
+}
+
+// ---- the walk summary of the batched polynomial kernels (gsgen_sh_batch_workspace_bytes_routed) ----------------------------------
+// What the one-wavefront-per-tile polynomial forward decides per list entry is wave-uniform -- has the tile saturated, does any
+// pixel see the entry, does the threshold guard trip -- and the backward of the same views decides the same from the same bits
+// (gauss_sh_pair, the explicit T update).  The forward therefore leaves, per (view, tile), one record of kWalkWords uint32 behind
+// the routing flags, and the polynomial backward of an unsegmented routed batch reads it instead of voting again:
+//   [0]                      walked: the number of list entries the entry loop reached before no pixel of the tile was alive
+//                            (the list's length if the tile never saturated)
+//   [1 + b], b < kWalkK      contributed: bit g = entry 32 b + g reached some pixel (wave_any(any_con))
+//   [1 + kWalkK + b]         guarded: bit g = the threshold guard tripped on entry 32 b + g
+// Bits of entries never reached are 0; the forward writes every word of the record of every tile it renders (the workspace may
+// arrive holding anything).  kWalkK = 8 words = 256 entries: the longest walk of the headline camera is 175 entries
+// (profiles/r06_notes.md section 8), and entries behind the cap are decided in the backward as before -- under the loop bound
+// `walked`, which holds for them too.
+constexpr int kWalkK = 8;
+constexpr int kWalkWords = 1 + 2 * kWalkK;
 
 // The Cholesky-form Gaussian (RGB / scalar / RGB + heads) of the two pixels (x, y2[0]), (x, y2[1]) of one lane: the
 // operation sequence of gauss_eval's non-SH branch element for element, without the threshold guard.  p0x = p0 * x.

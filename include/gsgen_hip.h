@@ -593,7 +593,19 @@ int gsgen_vol_render_backward_sh_bounded(uint32_t N, uint32_t D, const float *me
  * a tile, forward and backward alike: with sh_l1_bound given as well (the maximum gsgen_sh_l1_bound_rows leaves in out_max) a
  * view wholly within its bound -- the normal case -- takes the polynomial form without a look at the lists, otherwise the
  * tile's list is scanned against the per-splat bounds (any splat beyond them: the exact form for that tile).  sh_row_bounds == NULL: exactly the *_bounded behaviour on sh_l1_bound.  SH degree 3 only
- * (C != 4: the exact kernels).  No counterpart in the reference (vol_render_sh.h:48-65 evaluates the basis per pixel). */
+ * (C != 4: the exact kernels).  No counterpart in the reference (vol_render_sh.h:48-65 evaluates the basis per pixel).
+ *
+ * The walk summary.  Behind the flag bytes (padded to 16) gsgen_sh_batch_workspace_bytes_routed reserves 17 uint32 per (view, tile):
+ * `walked`, the number of list entries the polynomial forward's entry loop reached before no pixel of the tile was alive (the list's
+ * length if the tile never saturated); contributed[8], bit g of word b set when entry 32 b + g reached some pixel; guarded[8], the same
+ * for a trip of the threshold guard.  Bits of entries never reached are 0, and the forward writes every word of every tile it renders:
+ * the workspace may arrive holding anything.  A batched launch with per-splat bounds (sh_row_bounds), SH degree 3 and n_segments <= 1
+ * keeps it: gsgen_vol_render_sh_batch_routed writes the records of its views, and the polynomial kernel of
+ * gsgen_vol_render_backward_sh_batch_routed / _moments runs each tile's loop to `walked`, passes the entries nobody sees and takes the
+ * guard's trips from the bits instead of deciding again (entries behind the 256 of the bit words are decided there as before).  The
+ * summary a backward reads is the forward's, of the same views with the same inputs, in the same workspace; any number of backward
+ * launches may follow that forward.  Every other launch -- segmented, per-view bounds only, the exact kernels and their fallbacks, the
+ * per-camera entry points -- neither writes nor reads it.  Size the workspace with the function: the summary is part of it. */
 int gsgen_sh_l1_bound_rows(uint32_t N, const float *sh_coeffs, uint32_t C, float *out_max /* device, 1 float, or NULL */,
                            float *out_rows /* device, [N] */, gsgen_stream_t stream);
 /* The same without the 4-byte fill in front of the pass (one launch less per step): running_max is only ever RAISED -- an upper
