@@ -77,6 +77,25 @@ __device__ __forceinline__ bool wave_any(bool pred) {
   return __ballot((int)pred) != 0ull;
 #endif
 }
+// ---- lane masks -------------------------------------------------------------------------------------------------------------
+// A comparison leaves its result as a LANE MASK in a scalar register pair.  lane_mask(compare) names that mask as an integer, so
+// that per-pixel conditions are ANDed / ORed and voted on by the scalar unit, and lane_pred(mask) hands a mask back to the lanes
+// as the condition of a select -- both are free (no instruction).  The rule that keeps the entry loops' votes off the vector unit:
+// every flag that enters a vote is lane_mask(ONE comparison), formed in the basic block of its comparison; flags are combined as
+// masks; selects take lane_pred(mask).  The ballot of a boolean that is NOT a comparison's direct result (an `a | b`, or a flag
+// that crossed a branch) is materialised per lane -- v_cndmask 0 / 1 and a second compare, two vector instructions per vote that
+// compute nothing.  The CPU emulator runs a lane per fiber: there a "mask" is the lane's own flag and only the vote is collective.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef unsigned long long lane_mask_t;
+__device__ __forceinline__ lane_mask_t lane_mask(bool compare) { return __builtin_amdgcn_ballot_w64(compare); }
+__device__ __forceinline__ bool lane_pred(lane_mask_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ bool mask_any(lane_mask_t m) { return m != 0ull; }
+#else
+typedef bool lane_mask_t;
+__device__ __forceinline__ lane_mask_t lane_mask(bool compare) { return compare; }
+__device__ __forceinline__ bool lane_pred(lane_mask_t m) { return m; }
+__device__ __forceinline__ bool mask_any(lane_mask_t m) { return __ballot((int)m) != 0ull; }
+#endif
 // Orders the memory operations (LDS and global) of THIS wavefront's lanes: what any lane stored before the call is visible to
 // every lane of the same wavefront after it.  No s_barrier: correct wherever only one wavefront is involved -- including code
 // that the other wavefronts of the workgroup have already LEFT (a __syncthreads() there relies on the hardware dropping

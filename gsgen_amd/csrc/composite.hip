@@ -29,6 +29,13 @@
 // (fp64 / uncontracted fp32), so the discontinuous decision is the reference's.  Forward and
 // backward share eval code, so the backward's recomputed prefix equals the forward bit for
 // bit (the invariant the reference asserts at vol_render_sh.h:452-454).
+//
+// The polynomial SH entry loops (composite_fwd_sh_vec_tile / composite_bwd_sh_vec_tile, NB = 6) are bound by vector-instruction
+// issue; tools/kpath.py counts their ORDINARY path.  What keeps instructions that compute nothing off it:
+// votes are taken on lane masks -- lane_mask(ONE comparison), combined on the scalar unit, lane_pred(mask) for the selects
+// (common.hpp); the forward's trip count leaves its loop through readfirstlane, so the trip test is a scalar compare; the backward
+// takes the splat index once as a scalar and shifts it by the lane's geo_shift instead of multiplying per lane.  The record's
+// scalars are broadcast from the floats of Stage as before: staged as pairs they lose five copies and gain as many wait states.
 #include "composite_common.hpp"
 #include <stdio.h>
 #include <string.h>
@@ -715,7 +722,8 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
   uint32_t tay_mask = 0u;    // POLY: ... and those of the Taylor tier (no exponential per pixel: composite_common.hpp)
   int base = 0;
   for (; base < n; base += KB) {
-    const int nb = min(KB, n - base);
+    // (SUMMARY: the batch's bound from scalar operands, so that the entry loop's trip test is a scalar compare)
+    const int nb = SUMMARY ? min(KB, n - __builtin_amdgcn_readfirstlane(base)) : min(KB, n - base);
     uint32_t walk_con = 0u, walk_guard = 0u;
     if (base > 0) __syncthreads();  // everyone is done with the previous batch
     stage_batch<MODE, CB, NT, KB, true, !POLY>(S, p, st + base, nb);
@@ -751,10 +759,11 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
 
     int g = 0;  // (behind the loop: the number of this batch's entries the loop reached)
     for (; g < nb; ++g) {
-      bool any_alive = false;
+      // (the pixels' flags as lane masks, combined and voted on in scalar registers: common.hpp, "lane masks")
+      lane_mask_t al[PPL], any_alive = lane_mask_t();
 #pragma unroll
-      for (int j = 0; j < PPL; ++j) any_alive |= alive(j);
-      if (!wave_any(any_alive)) break;  // this wave's 64*PPL pixels are saturated
+      for (int j = 0; j < PPL; ++j) { al[j] = lane_mask(alive(j)); any_alive |= al[j]; }
+      if (!mask_any(any_alive)) break;  // this wave's 64*PPL pixels are saturated
       const int e_idx = base + g;
       if (seg_out && (e_idx % kSegLen) == 0 && e_idx > 0 && e_idx / kSegLen < p.nseg) {  // wave-uniform
 #pragma unroll
@@ -768,7 +777,7 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
       const float x = px - r_mx;
       // G2 / ag2: the Gaussian and a G, ZEROED where the pixel does not take part (skip threshold, not alive, or radial < 0)
       v2f G2[NP], ag2[NP], q2[NP];
-      bool any_con = false;
+      lane_mask_t any_con = lane_mask_t();
 #pragma unroll
       for (int jp = 0; jp < NP; ++jp) {
         G2[jp] = gauss_sh_pair(r_c0, r_c1, r_c2, r_c3, r_p0, x, py2[jp] - splat2(r_my), q2[jp]);
@@ -782,7 +791,7 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
         for (int jp = 0; jp < NP; ++jp)
 #pragma unroll
           for (int e = 0; e < 2; ++e)
-            if (alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
+            if (lane_pred(al[2 * jp + e]) && !(q2[jp][e] < 0.0f) && fabsf(ag2[jp][e] - kMinAlpha) <= kMinAlpha * kGuardTol) {
               G2[jp][e] = gauss_ref_f32(r_mx, r_my, r_c0, r_c1, r_c2, r_c3, px, py2[jp][e]);
               ag2[jp][e] = r_a * G2[jp][e];
             }
@@ -792,10 +801,11 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           // (radial < 0: gauss_eval's G = 0, which no pixel contributes with -- a term of the mask, see gauss_sh_pair)
-          const bool con = alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && !(ag2[jp][e] < kMinAlpha);
+          const lane_mask_t con_m = al[2 * jp + e] & lane_mask(!(q2[jp][e] < 0.0f)) & lane_mask(!(ag2[jp][e] < kMinAlpha));
+          const bool con = lane_pred(con_m);
           G2[jp][e] = con ? G2[jp][e] : 0.0f;
           if constexpr (!POLY) ag2[jp][e] = con ? ag2[jp][e] : 0.0f;
-          any_con |= con;
+          any_con |= con_m;
         }
       if constexpr (POLY) {  // the same products again, from the masked G: two packed multiplies instead of four selects
 #pragma unroll
@@ -803,7 +813,7 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
           ag2[jp] = splat2(r_a) * G2[jp];
         }
       }
-      const uint32_t contributed = wave_any_word(any_con);
+      const uint32_t contributed = mask_any_word(any_con);
       if constexpr (SUMMARY) {  // (scalar: two shifts and two ORs per entry)
         walk_con |= contributed << g;
         walk_guard |= guarded << g;
@@ -883,8 +893,11 @@ __device__ __forceinline__ void composite_fwd_sh_vec_tile(const CompParams &p, u
       }
     }
     if constexpr (SUMMARY) {
+      // (g through a scalar register: stored straight from the loop's counter, the value behind the loop is a VECTOR register's --
+      // the store is one lane's --, and with it the counter's bound and the trip test of every entry move to the vector unit)
+      const int g_end = __builtin_amdgcn_readfirstlane(g);
       if (walk_rec != nullptr && t == 0) {
-        walk_rec[0] = (uint32_t)(base + g);
+        walk_rec[0] = (uint32_t)(base + g_end);
         if (base < kWalkK * KB) {
           walk_rec[1 + base / KB] = walk_con;
           walk_rec[1 + kWalkK + base / KB] = walk_guard;
@@ -1425,7 +1438,7 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
   // stride per splat, nullptr for lanes that hold none -- three registers instead of the selects, shifts and spilled lane masks
   // that formed the address per entry (13 vector instructions per (wavefront, entry) less)
   float *geo_base = nullptr;
-  uint32_t geo_stride = 0u;
+  uint32_t geo_shift = 0u;  // log2 of the stride: 1, 2 or 4 floats per splat
   // POLY: the lane's column offset and its pixel pairs' row offsets stand for the six monomials (see the forward)
   const float pu = poly_offset(lx);
   const v2f pu2 = splat2(pu);
@@ -1443,14 +1456,14 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
       if (sep16_owner(lane)) {
         if (cls < 3 && slot == 6) {
           geo_base = cls == 0 ? p.g_mean : p.g_cov + (cls == 1 ? 0 : (MOM ? 2 : 3));
-          geo_stride = cls == 0 ? 2u : 4u;
+          geo_shift = cls == 0 ? 1u : 2u;
         } else if (cls == 3) {
           geo_base = slot == 0 ? p.g_mean + 1 : (slot == 1 ? p.g_cov + 1 : p.g_alpha);
-          geo_stride = slot == 0 ? 2u : (slot == 1 ? 4u : 1u);
+          geo_shift = slot == 0 ? 1u : (slot == 1 ? 2u : 0u);
         }
       } else if (!MOM && cls == 3 && slot == 1) {  // (lane & 1: the second holder of Mxy's slot)
         geo_base = p.g_cov + 2;
-        geo_stride = 4u;
+        geo_shift = 2u;
       }
     }
   } else {
@@ -1586,6 +1599,8 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             // (radial < 0: gauss_eval's G = 0, which no pixel contributes with -- a term of the mask, see gauss_sh_pair)
+            // (plain flags here: as lane masks -- the forward's form -- the pass on the summary keeps twelve masks alive at once and
+            // reloads spilled scalar registers nine times per entry)
             const bool con = alive(2 * jp + e) && !(q2[jp][e] < 0.0f) && !(ag2[jp][e] < kMinAlpha);
             G2[jp][e] = con ? G2[jp][e] : 0.0f;
             if constexpr (!POLY) ag2[jp][e] = con ? ag2[jp][e] : 0.0f;
@@ -1770,12 +1785,15 @@ __device__ __forceinline__ void composite_bwd_sh_vec_tile(const CompParams &p, u
                        v2f{rs[2][0], rs[2][1]}, v2f{rs[2][2], c3}, v2f{m1, c1}, v2f{ga, 0.0f}};
           const float tot = wave_reduce_scatter_sep16(t8, pu);
           const int comp = sep16_comp(lane);  // 8 * (channel, or 3 for the geometric class) + slot
-          const size_t id = (size_t)S.id[g];
+          // the splat's index ONCE, in a scalar register (an LDS broadcast: every lane read the same word): 48 * id and
+          // id << {0, 1, 2} are then the scalar unit's and a per-lane shift's, not 64-bit vector multiplies per lane and entry.
+          // 64-bit element offsets: valid for any N an int indexes.
+          const size_t id = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane(S.id[g]);
           // d L / d sh[c][k] = sum_r gw[c][r] V[r][k]: the 18 reduced values go through LDS, lanes (c, k) = (lane / 16,
           // lane % 16) expand them with their column of V (one wavefront per workgroup: the barrier is a wait)
           if (sep16_owner(lane) && comp < 3 * 8 && (comp & 7) < kPolyNB) gw_s[comp] = tot;
           // the geometric components, ONE atomic instruction (geo_base / geo_stride: the lane's slot, fixed before the loop)
-          if (geo_base != nullptr) atomicAdd(geo_base + id * geo_stride, tot);
+          if (geo_base != nullptr) atomicAdd(geo_base + (id << geo_shift), tot);
           __syncthreads();
           if (lane < 48) {
             const float *gw = &gw_s[(lane >> 4) * 8];

@@ -370,6 +370,17 @@ __device__ __forceinline__ uint32_t wave_any_word(bool pred) {
   return __ballot((int)pred) != 0ull ? 1u : 0u;
 #endif
 }
+// ... and of a lane mask (common.hpp, "lane masks"): the mask is in scalar registers already, no vector bool in between
+__device__ __forceinline__ uint32_t mask_any_word(lane_mask_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t c = (uint32_t)__builtin_popcountll(m);
+  uint32_t r;
+  asm("s_min_u32 %0, %1, 1" : "=s"(r) : "s"(c) : "scc");
+  return r;
+#else
+  return mask_any(m) ? 1u : 0u;
+#endif
+}
 // Does the threshold guard trip for this entry (wave-uniform, 0 / 1)?  ag2: a * (raw G) of the lane's pixel pairs, q2: their radial
 // numerators.  The answer is that of the per-pixel rule "a pixel with q >= 0 lies within kGuardTol of the skip threshold" (dead
 // pixels included: a spurious trip re-tests per pixel) -- with G zeroed where q < 0, as gauss_eval has it, such a pixel sits a whole
