@@ -75,18 +75,25 @@ __device__ __forceinline__ void stage_batch(Stage<MODE, CB, KB, WITH_COL> &S, co
       id = p.ids[list_base + t];
       const float2 m = *reinterpret_cast<const float2 *>(p.mean + 2 * (size_t)id);
       mx = m.x; my = m.y;
+      const float al_in = p.alpha[id];
+      // RGB / scalar / RGB + heads: a record with a non-finite mean or opacity never contributes.  a = 0 alone does not see to
+      // that: 0 * G is NaN for the G of a non-finite offset, and !(NaN < 1/255) takes the entry; and fminf(NaN, 0.99) is 0.99,
+      // a near-opaque layer.  Such a record is staged with a = 0, a zero factor AND a zero mean (G = 1, a G = 0: skipped).
+      bool live = true;
+      if constexpr (MODE != MODE_SH) live = finite_f(mx) && finite_f(my) && (al_in == al_in);
       if (prepared) {
         // the record the projection launch prepared for this (view, Gaussian) (gsgen_geometry_view::chol): no fp64 chain here
         const float4 q = *reinterpret_cast<const float4 *>(p.chol + 4 * (size_t)id);
-        const float al = fminf(p.alpha[id], kAlphaClamp);
-        const bool ok = q.w != 0.0f && finite_f(mx) && finite_f(my) && finite_f(al);
+        const float al = fminf(al_in, kAlphaClamp);
+        const bool ok = q.w != 0.0f && live && finite_f(al);
         a = ok ? al : 0.0f; p0 = ok ? q.x : 0.0f; p1 = ok ? q.y : 0.0f; p2 = ok ? q.z : 0.0f;
       } else {
         const float4 c = *reinterpret_cast<const float4 *>(p.cov + 4 * (size_t)id);
         c0 = c.x; c1 = c.y; c2 = c.z; c3 = c.w;
-        const GRec r = prep_record<MODE>(mx, my, c0, c1, c2, c3, p.alpha[id]);
-        a = r.a; p0 = r.p0; p1 = r.p1; p2 = r.p2;
+        const GRec r = prep_record<MODE>(mx, my, c0, c1, c2, c3, al_in);
+        a = live ? r.a : 0.0f; p0 = live ? r.p0 : 0.0f; p1 = live ? r.p1 : 0.0f; p2 = live ? r.p2 : 0.0f;
       }
+      if (!live) { mx = 0.0f; my = 0.0f; }
     }
     S.id[t] = id; S.mx[t] = mx; S.my[t] = my; S.a[t] = a;
     if (!prepared) { S.c0[t] = c0; S.c1[t] = c1; S.c2[t] = c2; S.c3[t] = c3; }  // (prepared: the guard path reads cov from memory)
