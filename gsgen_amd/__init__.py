@@ -13,7 +13,8 @@
                          and its Pearson depth loss (depth_loss, pearson_depth_loss, pearson_depth_loss_terms)
     gsgen_amd.background the learned MLP background of conf/renderer/mlp_bg.yaml fused with its composite (MLPBackground, mlp_background,
                          mlp_background_images, mlp_background_over)
-    gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt)
+    gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt), with vertex
+                         normals and colours from the same field (vertex_attributes, colored_density_mesh, colored_mesh_from_ckpt)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
 There is no CPU implementation in this package: every entry point needs the HIP library and
@@ -37,7 +38,8 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name == "mesh":
         import importlib
         return importlib.import_module(".mesh", __name__)
-    if name in ("marching_cubes", "marching_cubes_into", "density_mesh", "mesh_from_ckpt"):
+    if name in ("marching_cubes", "marching_cubes_into", "density_mesh", "mesh_from_ckpt", "vertex_attributes", "colored_density_mesh",
+                "colored_mesh_from_ckpt"):
         from . import mesh
         return getattr(mesh, name)
     raise AttributeError(name)

@@ -27,7 +27,7 @@
 //      and the grid only while the box is within its K-th distance.  Every bound is shrunk by a margin that covers the rounding
 //      of the cell assignment, so pruning never drops a candidate that could enter the list.
 //
-// Steps 1-3 are the INDEX over `points` (build_index, in knn_index.hpp beside this file: fps.hip builds the same index); step 4 is one of three consumers of it:
+// Steps 1-3 are the INDEX over `points` (build_index, in knn_index.hpp beside this file: fps.hip builds the same index); step 4 is one of four consumers of it:
 //   k_knn_query       every point is a query (gsgen_knn, above).
 //   k_knn_query_ext   queries from an array of their own, in the caller's order (gsgen_knn_query): d = p_j - q.  The query's cell
 //                     comes from the index's Params; a query outside the grid box takes the outlier-query path, a non-finite
@@ -36,6 +36,8 @@
 //                     lattice points, runs the same search and sums opacity_j exp(-1/2 d^T Sigma_j^-1 d) over the neighbours it
 //                     keeps, straight from the top-K in registers: one store per lattice point, no idx / dist2 in memory.
 //                     Sigma^-1 = R diag(1 / s^2) R^T in closed form, once per Gaussian (k_density_prep).
+//   k_density_points  the same search and sum at points of the caller's own, one lane per point as k_knn_query_ext, with the sum's
+//                     gradient and a density-weighted colour beside its value (gsgen_density_points: mesh vertex normals and colours).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -244,8 +246,13 @@ __global__ void __launch_bounds__(kBlock) k_knn_query_ext(uint32_t Q, uint32_t K
 // rec[2 i] = (a00, a01, a02, a11), rec[2 i + 1] = (a12, a22, opacity, 0): A = Sigma^-1 = R diag(1 / s^2) R^T, R the rotation of
 // geometry.hip's quat_to_rot (kornia 0.6.0, w first, normalised with eps 1e-12), Sigma = R diag(s^2) R^T as qsvec2covmat_batched
 // builds it.  A_ij = (R_i0 R_j0) w_0 + (R_i1 R_j1) w_1 + (R_i2 R_j2) w_2, w_k = 1 / (s_k s_k), left to right.
+// rec_g (null for the lattice, which reads rec alone): the same six entries for the GRADIENT of the point kernel, the formula
+// evaluated in fp64 from the fp32 inputs and rounded to fp32 once: rec_g[2 i] = (a00, a01, a02, a11), rec_g[2 i + 1] = (a12, a22, 0, 0).
+// An fp32 off-diagonal entry that is the remainder of three cancelling terms carries hundreds of eps of its own size (the errors of
+// R are absolute); m = d^T A d does not feel that, its diagonal dominates, but a row of A d does.  rec itself does not change by a bit.
 __global__ void __launch_bounds__(kBlock) k_density_prep(uint32_t N, const float *__restrict__ qvec, const float *__restrict__ scale,
-                                                          const float *__restrict__ opacity, float4 *__restrict__ rec) {
+                                                          const float *__restrict__ opacity, float4 *__restrict__ rec,
+                                                          float4 *__restrict__ rec_g) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= N) return;
   const float *q = qvec + 4 * (size_t)i, *sc = scale + 3 * (size_t)i;
@@ -267,11 +274,39 @@ __global__ void __launch_bounds__(kBlock) k_density_prep(uint32_t N, const float
     for (int b = a; b < 3; ++b) A[a][b] = R[a][0] * R[b][0] * w0 + R[a][1] * R[b][1] * w1 + R[a][2] * R[b][2] * w2;
   rec[2 * (size_t)i] = make_float4(A[0][0], A[0][1], A[0][2], A[1][1]);
   rec[2 * (size_t)i + 1] = make_float4(A[1][2], A[2][2], opacity[i], 0.0f);
+  if (rec_g != nullptr) {
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    double nd = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    nd = nd > 1e-12 ? nd : 1e-12;
+    const double dw = q0 / nd, dx = q1 / nd, dy = q2 / nd, dz = q3 / nd;
+    const double Rd[3][3] = {{1.0 - 2.0 * (dy * dy + dz * dz), 2.0 * (dx * dy - dw * dz), 2.0 * (dx * dz + dw * dy)},
+                             {2.0 * (dx * dy + dw * dz), 1.0 - 2.0 * (dx * dx + dz * dz), 2.0 * (dy * dz - dw * dx)},
+                             {2.0 * (dx * dz - dw * dy), 2.0 * (dy * dz + dw * dx), 1.0 - 2.0 * (dx * dx + dy * dy)}};
+    const double s0 = sc[0], s1 = sc[1], s2 = sc[2];
+    const double v0 = 1.0 / (s0 * s0), v1 = 1.0 / (s1 * s1), v2 = 1.0 / (s2 * s2);
+    float G[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = a; b < 3; ++b) G[a][b] = (float)(Rd[a][0] * Rd[b][0] * v0 + Rd[a][1] * Rd[b][1] * v1 + Rd[a][2] * Rd[b][2] * v2);
+    rec_g[2 * (size_t)i] = make_float4(G[0][0], G[0][1], G[0][2], G[1][1]);
+    rec_g[2 * (size_t)i + 1] = make_float4(G[1][2], G[2][2], 0.0f, 0.0f);
+  }
+}
+
+// One term of the field, shared by the lattice and the point kernels: t = opacity_j exp(-1/2 m),
+// m = a00 dx dx + a11 dy dy + a22 dz dz + 2 (a01 dx dy + a02 dx dz + a12 dy dz), d = q - mean_j, every product left to right.
+__device__ __forceinline__ float density_term(const float4 q, const float *__restrict__ mean, const float4 r0, const float4 r1,
+                                              uint32_t j, float &dx, float &dy, float &dz) {
+  dx = q.x - mean[3 * (size_t)j], dy = q.y - mean[3 * (size_t)j + 1], dz = q.z - mean[3 * (size_t)j + 2];
+  const float diag = r0.x * dx * dx + r0.w * dy * dy + r1.y * dz * dz;
+  const float off = r0.y * dx * dy + r0.z * dx * dz + r1.x * dy * dz;
+  const float m = diag + 2.0f * off;
+  return r1.z * expf(-0.5f * m);
 }
 
 // A 256-thread workgroup = four wavefronts = four 4 x 4 x 4 bricks (z fastest, as the output is laid out); lanes past nx, ny or nz
 // idle.  Kept neighbours: entries skip .. skip + K - 1 of the sorted list; a padded entry (index -1) contributes nothing.
-// m = a00 dx dx + a11 dy dy + a22 dz dz + 2 (a01 dx dy + a02 dx dz + a12 dy dz), d = q - mean_j, every product left to right.
 template <int L>
 __global__ void __launch_bounds__(kBlock) k_density_grid(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t K, uint32_t skip, uint32_t cap,
                                                           const Params *__restrict__ P, const uint32_t *__restrict__ start,
@@ -295,14 +330,88 @@ __global__ void __launch_bounds__(kBlock) k_density_grid(uint32_t nx, uint32_t n
     const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
     if ((uint32_t)k >= skip && (uint32_t)k < K + skip && j != 0xffffffffu) {
       const float4 r0 = rec[2 * (size_t)j], r1 = rec[2 * (size_t)j + 1];
-      const float dx = q.x - mean[3 * (size_t)j], dy = q.y - mean[3 * (size_t)j + 1], dz = q.z - mean[3 * (size_t)j + 2];
-      const float diag = r0.x * dx * dx + r0.w * dy * dy + r1.y * dz * dz;
-      const float off = r0.y * dx * dy + r0.z * dx * dz + r1.x * dy * dz;
-      const float m = diag + 2.0f * off;
-      sum += r1.z * expf(-0.5f * m);
+      float dx, dy, dz;
+      sum += density_term(q, mean, r0, r1, j, dx, dy, dz);
     }
   }
   out[((size_t)ix * ny + iy) * nz + iz] = sum;
+}
+
+// --- 4d. the field at points of the caller's own ---------------------------------------------------------------------------
+// The lattice kernel's search and sum at any position, in the launch shape of k_knn_query_ext: one lane per query, in the caller's
+// order, the list in registers.  Per query, over the Ks = K + skip entries of the list (a padded entry contributes nothing):
+//   t_k = density_term (above), g = A d row by row, left to right: gx = (a00 dx + a01 dy) + a02 dz, gy = (a01 dx + a11 dy) + a12 dz,
+//   gz = (a02 dx + a12 dy) + a22 dz, with A from rec_g (k_density_prep: the entries rounded once from fp64; t_k takes rec's).
+//   density = sum of t_k, grad_a = sum of -(t_k g_ka), both over the entries skip .. skip + K - 1 in list order from 0.0f (the
+//   gradient of the sum with the neighbour set held fixed; x - y and x + (-y) are the same bits);
+//   rgb_c = num_c / den with num_c = sum of t_k color_j[c], den = sum of t_k over ALL entries 0 .. Ks - 1 in list order (the nearest
+//   centre counts even where the field drops it); den < 2^-126: the colour of list entry 0, copied.
+// A non-finite query, and for rgb a list without a single centre, write 0.  density / grad / rgb / color may be null: a test that is
+// uniform over the launch; an output that is not wanted costs nothing and does not change the bits of the others.
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_density_points(uint32_t Q, uint32_t K, uint32_t skip, uint32_t cap, const Params *__restrict__ P,
+                                                            const uint32_t *__restrict__ start, const float4 *__restrict__ sorted,
+                                                            const float *__restrict__ mean, const float4 *__restrict__ rec,
+                                                            const float4 *__restrict__ rec_g, const float *__restrict__ color,
+                                                            const float *__restrict__ points,
+                                                            float *__restrict__ density, float *__restrict__ grad,
+                                                            float *__restrict__ rgb) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= Q) return;
+  const float4 q = make_float4(points[3 * (size_t)t], points[3 * (size_t)t + 1], points[3 * (size_t)t + 2], 0.0f);
+  unsigned long long list[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) list[k] = kPad;
+  search_ext<L>(list, cap, P, start, sorted, q);
+  float sum = 0.0f, gx = 0.0f, gy = 0.0f, gz = 0.0f;
+  float nr = 0.0f, ng = 0.0f, nb = 0.0f, den = 0.0f;
+  const bool field = density != nullptr || grad != nullptr;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+    const bool kept = (uint32_t)k >= skip && field;
+    if ((uint32_t)k < K + skip && j != 0xffffffffu && (kept || rgb != nullptr)) {
+      const float4 r0 = rec[2 * (size_t)j], r1 = rec[2 * (size_t)j + 1];
+      float dx, dy, dz;
+      const float tk = density_term(q, mean, r0, r1, j, dx, dy, dz);
+      if (kept) {
+        sum += tk;
+        if (grad != nullptr) {
+          const float4 g0 = rec_g[2 * (size_t)j], g1 = rec_g[2 * (size_t)j + 1];
+          const float ax = g0.x * dx + g0.y * dy + g0.z * dz;
+          const float ay = g0.y * dx + g0.w * dy + g1.x * dz;
+          const float az = g0.z * dx + g1.x * dy + g1.y * dz;
+          gx -= tk * ax;
+          gy -= tk * ay;
+          gz -= tk * az;
+        }
+      }
+      if (rgb != nullptr) {
+        nr += tk * color[3 * (size_t)j];
+        ng += tk * color[3 * (size_t)j + 1];
+        nb += tk * color[3 * (size_t)j + 2];
+        den += tk;
+      }
+    }
+  }
+  if (density != nullptr) density[t] = sum;
+  if (grad != nullptr) {
+    grad[3 * (size_t)t] = gx;
+    grad[3 * (size_t)t + 1] = gy;
+    grad[3 * (size_t)t + 2] = gz;
+  }
+  if (rgb != nullptr) {
+    const uint32_t j0 = (uint32_t)(list[0] & 0xffffffffull);
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+    if (den >= 1.17549435e-38f) {
+      r = nr / den, g = ng / den, b = nb / den;
+    } else if (j0 != 0xffffffffu) {
+      r = color[3 * (size_t)j0], g = color[3 * (size_t)j0 + 1], b = color[3 * (size_t)j0 + 2];
+    }
+    rgb[3 * (size_t)t] = r;
+    rgb[3 * (size_t)t + 1] = g;
+    rgb[3 * (size_t)t + 2] = b;
+  }
 }
 
 template <int L>
@@ -324,6 +433,14 @@ inline void launch_density(uint32_t blocks, uint32_t nx, uint32_t ny, uint32_t n
                            hipStream_t s) {
   hipLaunchKernelGGL((k_density_grid<L>), dim3(blocks), dim3(kBlock), 0, s, nx, ny, nz, K, skip, cap, (const Params *)w.P,
                      (const uint32_t *)w.start, (const float4 *)w.sorted, mean, rec, ax, ay, az, out);
+}
+
+template <int L>
+inline void launch_density_points(uint32_t Q, uint32_t K, uint32_t skip, uint32_t cap, const Ws &w, const float *mean, const float4 *rec,
+                                  const float4 *rec_g, const float *color, const float *points, float *density, float *grad, float *rgb, hipStream_t s) {
+  hipLaunchKernelGGL((k_density_points<L>), dim3((uint32_t)(((uint64_t)Q + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, Q, K, skip, cap,
+                     (const Params *)w.P, (const uint32_t *)w.start, (const float4 *)w.sorted, mean, rec, rec_g, color, points, density,
+                     grad, rgb);
 }
 
 // the records of k_density_prep behind the index's workspace
@@ -410,7 +527,7 @@ int gsgen_density_grid(const float *mean, const float *qvec, const float *scale,
   float4 *rec = (float4 *)((char *)w.P + density_rec_offset(N, K));
   const uint32_t cap = cell_cap(N, Ks);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_density_prep, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, qvec, scale, opacity, rec);
+  hipLaunchKernelGGL(k_density_prep, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, qvec, scale, opacity, rec, (float4 *)nullptr);
   if (int e = build_index(mean, N, Ks, w, s)) return e;
   const uint32_t blocks = (uint32_t)((bricks + kBlock / 64 - 1) / (kBlock / 64));
   if (Ks <= 1) launch_density<1>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
@@ -419,6 +536,40 @@ int gsgen_density_grid(const float *mean, const float *qvec, const float *scale,
   else if (Ks <= 8) launch_density<8>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
   else if (Ks <= 16) launch_density<16>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
   else launch_density<32>(blocks, nx, ny, nz, K, skip_nearest, cap, w, mean, rec, axis_x, axis_y, axis_z, out, s);
+  return (int)hipGetLastError();
+}
+
+size_t gsgen_density_points_workspace_bytes(uint32_t n_points, uint32_t K) {
+  // (the lattice's layout, then the gradient's records)
+  const size_t grid = gsgen_density_grid_workspace_bytes(n_points, K);
+  return grid == 0 ? 0 : grid + align256(2 * sizeof(float4) * (size_t)n_points);
+}
+
+int gsgen_density_points(const float *mean, const float *qvec, const float *scale, const float *opacity, const float *color, uint32_t N,
+                         const float *points, uint32_t Q, uint32_t K, uint32_t skip_nearest, float *density, float *grad, float *rgb,
+                         void *workspace, size_t workspace_bytes, gsgen_stream_t stream) {
+  if (skip_nearest > 1) return GSGEN_EINVAL;
+  const uint32_t Ks = K + skip_nearest;  // the list that is searched
+  if (K == 0 || K > 32 || Ks > 32) return GSGEN_EUNSUPPORTED;
+  if (N == 0 || Ks > N || N > 0x7fffffffu) return GSGEN_EINVAL;
+  if (rgb && !color) return GSGEN_EINVAL;
+  if (Q == 0) return 0;
+  if (!mean || !qvec || !scale || !opacity || !points || !workspace) return GSGEN_EINVAL;
+  if (gsgen_density_points_workspace_bytes(N, K) > workspace_bytes) return GSGEN_EWORKSPACE;
+  if (!density && !grad && !rgb) return 0;  // (nothing asked for)
+  const Ws w = carve(workspace, N, Ks);
+  float4 *rec = (float4 *)((char *)w.P + density_rec_offset(N, K));  // (the lattice's layout)
+  float4 *rec_g = (float4 *)((char *)rec + align256(2 * sizeof(float4) * (size_t)N));
+  const uint32_t cap = cell_cap(N, Ks);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_density_prep, dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, qvec, scale, opacity, rec, rec_g);
+  if (int e = build_index(mean, N, Ks, w, s)) return e;
+  if (Ks <= 1) launch_density_points<1>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
+  else if (Ks <= 2) launch_density_points<2>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
+  else if (Ks <= 4) launch_density_points<4>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
+  else if (Ks <= 8) launch_density_points<8>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
+  else if (Ks <= 16) launch_density_points<16>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
+  else launch_density_points<32>(Q, K, skip_nearest, cap, w, mean, rec, rec_g, color, points, density, grad, rgb, s);
   return (int)hipGetLastError();
 }
 

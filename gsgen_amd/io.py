@@ -2,7 +2,8 @@
 (trainer.py:255-266), the 17-field float32 `.ply` (utils/export.py:157-203) and the 32-byte-record
 `.splat` of the web viewer sorted by volume * opacity (utils/export.py:206-283).  Host code only,
 vectorised (the reference packs record by record with struct.pack); byte-identical output.  Also the
-Wavefront `.obj` that `to_mesh` writes through mcubes.export_obj (utils/export.py:123-155).
+Wavefront `.obj` that `to_mesh` writes through mcubes.export_obj (utils/export.py:123-155), with optional vertex normals and colours
+(gsgen_amd.mesh.vertex_attributes), and the same mesh as a binary `.ply` (write_ply_mesh).
 
 `params` is the dict the reference saves under "params": raw (pre-activation) tensors or arrays
 mean [N,3], qvec [N,4] (w,x,y,z), svec [N,3] (log scale), color [N,3] (logit), alpha [N] (logit).
@@ -117,18 +118,40 @@ def read_splat(path):
 
 
 # ---- .obj -----------------------------------------------------------------------------------------
-def write_obj(path, verts, tris):
-    """`v x y z` lines, then `f a b c` lines with 1-based vertex indices, no normals: the layout of mcubes.export_obj.  verts [V,3]
-    and tris [F,3] are tensors or arrays.  Coordinates are written with 9 significant digits, which identify a float32: read_obj
-    returns the same bits."""
-    v = verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts
-    t = tris.detach().cpu().numpy() if hasattr(tris, "detach") else tris
-    v, t = np.asarray(v, np.float32).reshape(-1, 3), np.asarray(t, np.int64).reshape(-1, 3)
+def _mesh_arrays(who, verts, tris, normals, colors):
+    """host arrays of a mesh, checked: verts [V,3] float32, tris [F,3] int64, normals / colors [V,3] float32 or None"""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else a  # noqa: E731
+    v, t = np.asarray(host(verts), np.float32).reshape(-1, 3), np.asarray(host(tris), np.int64).reshape(-1, 3)
     if len(t) and (t.min() < 0 or t.max() >= len(v)):
-        raise ValueError(f"gsgen_amd.io.write_obj: triangle indices {t.min()}..{t.max()} for {len(v)} vertices")
+        raise ValueError(f"gsgen_amd.io.{who}: triangle indices {t.min()}..{t.max()} for {len(v)} vertices")
+    attrs = []
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None:
+            a = np.asarray(host(a), np.float32).reshape(-1, 3)
+            if len(a) != len(v):
+                raise ValueError(f"gsgen_amd.io.{who}: {len(a)} {name} for {len(v)} vertices")
+        attrs.append(a)
+    return v, t, attrs[0], attrs[1]
+
+
+def write_obj(path, verts, tris, normals=None, colors=None):
+    """`v x y z` lines, then `f a b c` lines with 1-based vertex indices: the layout of mcubes.export_obj.  verts [V,3] and tris
+    [F,3] are tensors or arrays.  Coordinates are written with 9 significant digits, which identify a float32: read_obj returns the
+    same bits.  colors [V,3] go on the vertex line, `v x y z r g b`, clipped to [0, 1] (the widely read extension of the format);
+    normals [V,3] go as `vn` lines after the vertices, one per vertex, and the faces become `f a//a b//b c//c`.  With neither, the
+    file is what mcubes.export_obj writes."""
+    v, t, n, c = _mesh_arrays("write_obj", verts, tris, normals, colors)
     with open(path, "w") as f:
-        f.write("".join("v %.9g %.9g %.9g\n" % (x, y, z) for x, y, z in v.astype(np.float64).tolist()))
-        f.write("".join("f %d %d %d\n" % (a, b, c) for a, b, c in (t + 1).tolist()))
+        if c is None:
+            f.write("".join("v %.9g %.9g %.9g\n" % (x, y, z) for x, y, z in v.astype(np.float64).tolist()))
+        else:
+            vc = np.concatenate((v, np.clip(c, np.float32(0), np.float32(1))), axis=1).astype(np.float64)
+            f.write("".join("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(row) for row in vc.tolist()))
+        if n is None:
+            f.write("".join("f %d %d %d\n" % (a, b, c) for a, b, c in (t + 1).tolist()))
+        else:
+            f.write("".join("vn %.9g %.9g %.9g\n" % (x, y, z) for x, y, z in n.astype(np.float64).tolist()))
+            f.write("".join("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (t + 1).tolist()))
 
 
 def read_obj(path):
@@ -147,3 +170,95 @@ def read_obj(path):
                     raise ValueError(f"gsgen_amd.io.read_obj: {path}: a face of {len(p) - 1} vertices (triangles only)")
                 t.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
     return np.asarray(v, np.float64).reshape(-1, 3).astype(np.float32), np.asarray(t, np.int64).reshape(-1, 3)
+
+
+def read_obj_attributes(path):
+    """-> (verts float32 [V,3], tris int64 [F,3], normals float32 [V,3] or None, colors float32 [V,3] or None) of a file that
+    write_obj wrote: colours from `v x y z r g b` lines (all vertices or none), normals from `vn` lines through the faces'
+    `a//a` entries, which must name the vertex's own normal (one normal per vertex)"""
+    v, c, n, t = [], [], [], []
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                v.append([float(x) for x in p[1:4]])
+                if len(p) >= 7:
+                    c.append([float(x) for x in p[4:7]])
+            elif p[0] == "vn":
+                n.append([float(x) for x in p[1:4]])
+            elif p[0] == "f":
+                if len(p) != 4:
+                    raise ValueError(f"gsgen_amd.io.read_obj_attributes: {path}: a face of {len(p) - 1} vertices (triangles only)")
+                for x in p[1:4]:
+                    s = x.split("/")
+                    if len(s) == 3 and s[2] != s[0]:
+                        raise ValueError(f"gsgen_amd.io.read_obj_attributes: {path}: face entry {x}: normals are per vertex here")
+                t.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
+    if (c and len(c) != len(v)) or (n and len(n) != len(v)):
+        raise ValueError(f"gsgen_amd.io.read_obj_attributes: {path}: {len(c)} colours and {len(n)} normals for {len(v)} vertices")
+    arr = lambda a: np.asarray(a, np.float64).reshape(-1, 3).astype(np.float32)  # noqa: E731
+    return arr(v), np.asarray(t, np.int64).reshape(-1, 3), arr(n) if n else None, arr(c) if c else None
+
+
+# ---- mesh .ply --------------------------------------------------------------------------------------
+def _ply_mesh_dtypes(has_normals, has_colors):
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if has_normals:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if has_colors:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    return np.dtype(fields), np.dtype([("n", "u1"), ("idx", "<i4", 3)])
+
+
+def write_ply_mesh(path, verts, tris, normals=None, colors=None):
+    """binary_little_endian PLY of a triangle mesh: element vertex with float x y z, float nx ny nz when normals are given, uchar
+    red green blue when colors are given (round(clip(c, 0, 1) * 255)); element face with `list uchar int vertex_indices`.  What
+    MeshLab, Blender and Open3D read; nothing third-party."""
+    v, t, n, c = _mesh_arrays("write_ply_mesh", verts, tris, normals, colors)
+    if len(t) and t.max() > 0x7fffffff:
+        raise ValueError("gsgen_amd.io.write_ply_mesh: vertex indices beyond int32")
+    vdt, fdt = _ply_mesh_dtypes(n is not None, c is not None)
+    vt = np.empty(len(v), vdt)
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        vt["nx"], vt["ny"], vt["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if c is not None:
+        u8 = np.rint(np.clip(np.nan_to_num(c.astype(np.float64), nan=0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+        vt["red"], vt["green"], vt["blue"] = u8[:, 0], u8[:, 1], u8[:, 2]
+    ft = np.empty(len(t), fdt)
+    ft["n"], ft["idx"] = 3, t
+    kinds = {"<f4": "float", "u1": "uchar", "|u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property {kinds[vdt[name].str]} {name}" for name in vdt.names]
+    header += [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vt.tobytes())
+        f.write(ft.tobytes())
+
+
+def read_ply_mesh(path):
+    """-> (verts float32 [V,3], tris int64 [F,3], normals float32 [V,3] or None, colors uint8 [V,3] or None): the inverse of
+    write_ply_mesh (triangles only; the property sets it writes)"""
+    with open(path, "rb") as f:
+        blob = f.read()
+    end = blob.index(b"end_header\n") + len(b"end_header\n")
+    lines = blob[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or "binary_little_endian" not in lines[1]:
+        raise ValueError("not a binary little-endian PLY")
+    nv = int([ln for ln in lines if ln.startswith("element vertex")][0].split()[2])
+    nf = int([ln for ln in lines if ln.startswith("element face")][0].split()[2])
+    props = [tuple(ln.split()[1:]) for ln in lines if ln.startswith("property") and not ln.startswith("property list")]
+    has_n, has_c = ("float", "nx") in props, ("uchar", "red") in props
+    vdt, fdt = _ply_mesh_dtypes(has_n, has_c)
+    if [p[1] for p in props] != list(vdt.names) or "property list uchar int vertex_indices" not in lines:
+        raise ValueError(f"gsgen_amd.io.read_ply_mesh: {path}: unexpected properties {props}")
+    vt = np.frombuffer(blob, vdt, count=nv, offset=end)
+    ft = np.frombuffer(blob, fdt, count=nf, offset=end + nv * vdt.itemsize)
+    if nf and (ft["n"] != 3).any():
+        raise ValueError(f"gsgen_amd.io.read_ply_mesh: {path}: triangles only")
+    col = lambda names: np.stack([vt[k] for k in names], 1)  # noqa: E731
+    return (col(("x", "y", "z")), ft["idx"].astype(np.int64).reshape(-1, 3), col(("nx", "ny", "nz")) if has_n else None,
+            col(("red", "green", "blue")) if has_c else None)

@@ -4,6 +4,8 @@ gsgen_amd.density goes to triangles without leaving the device, and gsgen_amd.io
 
     verts, tris, L = mesh_from_ckpt(ckpt)          # ckpt: the raw fields on the GPU (gsgen_amd.io.load_checkpoint(..., "cuda")[0])
     gsgen_amd.io.write_obj("mesh.obj", verts, tris)
+    verts, tris, normals, colors, L = colored_mesh_from_ckpt(ckpt)     # + vertex normals and colours (vertex_attributes)
+    gsgen_amd.io.write_obj("mesh.obj", verts, tris, normals, colors)   # or write_ply_mesh
 
 Conventions (DESIGN.md "Marching cubes"): a lattice point is inside iff grid - thresh > 0 in fp32 (NaN is outside), as in the
 reference's in-tree shap_e/rendering/mc.py, against which the kernels are pinned.  PyMCubes is not available to pin against: its
@@ -123,3 +125,44 @@ def mesh_from_ckpt(ckpt, reso=128, K=3, thresh=0.5, L=-1.0):
     grid, L = get_density_val_grid_from_ckpt(ckpt, L=L, reso=reso, K=K)
     verts, tris = marching_cubes(grid, thresh)
     return index_to_world(verts, L, reso), tris, L
+
+
+@torch.no_grad()
+def vertex_attributes(verts, mean, qvec, scale, opacity, color=None, K=3, skip_nearest=True):
+    """-> (normals [V,3], colors [V,3] or None) of mesh vertices in WORLD coordinates, from the field they were meshed from
+    (gsgen_amd.density.field_at: one fused launch).  normal = -grad / |grad|: from high density to low, the side the triangles'
+    winding faces; a zero or non-finite gradient gives a zero normal.  colors (when color [N,3] is given): the field's
+    term-weighted average over the K + skip_nearest nearest centres.  Use the (K, skip_nearest) of the field that was meshed:
+    DESIGN.md "Vertex normals and colours".  No vertices: empty tensors, no launch."""
+    from .density import field_at
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"gsgen_amd.mesh: verts must be [V, 3], got {tuple(verts.shape)}")
+    if verts.shape[0] == 0:
+        empty = torch.empty(0, 3, device=mean.device, dtype=torch.float32)
+        return empty, (None if color is None else empty.clone())
+    _, grad, rgb = field_at(mean, qvec, scale, opacity, verts, K, skip_nearest, color=color, density=False, grad=True)
+    big = grad.abs().amax(dim=1, keepdim=True)  # (scaled first: the squares of a tiny gradient must not underflow)
+    ok = torch.isfinite(big) & (big > 0)
+    g = grad / torch.where(ok, big, torch.ones_like(big))
+    normals = torch.where(ok, -g / g.norm(dim=1, keepdim=True), torch.zeros_like(grad))
+    return normals, rgb
+
+
+@torch.no_grad()
+def colored_density_mesh(mean, qvec, scale, opacity, color, L, reso, K=3, thresh=0.5, skip_nearest=True):
+    """density_mesh with vertex_attributes of the same field -> (verts [V,3] world, tris [F,3] int32, normals [V,3], colors [V,3]);
+    color [N,3] activated"""
+    verts, tris = density_mesh(mean, qvec, scale, opacity, L, reso, K, thresh, skip_nearest)
+    normals, colors = vertex_attributes(verts, mean, qvec, scale, opacity, color, K, skip_nearest)
+    return verts, tris, normals, colors
+
+
+@torch.no_grad()
+def colored_mesh_from_ckpt(ckpt, reso=128, K=3, thresh=0.5, L=-1.0):
+    """mesh_from_ckpt with vertex normals and colours -> (verts, tris, normals, colors, L).  ckpt also holds the raw "color";
+    colours are sigmoid(color), as to_splat activates them (utils/export.py:254).  Write the result with
+    gsgen_amd.io.write_obj(path, verts, tris, normals, colors) or write_ply_mesh."""
+    verts, tris, L = mesh_from_ckpt(ckpt, reso=reso, K=K, thresh=thresh, L=L)
+    normals, colors = vertex_attributes(verts, ckpt["mean"], ckpt["qvec"], torch.exp(ckpt["svec"]), torch.sigmoid(ckpt["alpha"]),
+                                        torch.sigmoid(ckpt["color"]), K, True)
+    return verts, tris, normals, colors, L

@@ -709,6 +709,26 @@ class GaussianSplattingRenderer(nn.Module):
             L = self.mean.abs().max().item() * 1.1
         return density_grid(self.mean, self.qvec, self.svec, self.alpha, L, reso, K, True)
 
+    @torch.no_grad()
+    def to_mesh(self, reso=128, K=3, thresh=0.5, L=-1.0, path=None):
+        """utils/export.py:123-155 (`to_mesh`) from the model's activated fields, with vertex normals and colours ->
+        (verts [V,3] world, tris [F,3] int32, normals [V,3], colors [V,3], L): gsgen_amd.mesh.colored_density_mesh on the field
+        of get_density_val_grid.  L < 0: mean.abs().max() * 1.1 (one host sync).  path: also written there, `.obj`
+        (gsgen_amd.io.write_obj) or `.ply` (write_ply_mesh) by its suffix."""
+        import os
+        from . import io as GIO
+        from .mesh import colored_density_mesh
+        if L < 0.0:
+            L = self.mean.abs().max().item() * 1.1
+        verts, tris, normals, colors = colored_density_mesh(self.mean, self.qvec, self.svec, self.alpha, self.color, L, reso, K,
+                                                            thresh, True)
+        if path is not None:
+            suffix = os.path.splitext(str(path))[1].lower()
+            if suffix not in (".obj", ".ply"):
+                raise ValueError(f"gsgen_amd.model: to_mesh writes .obj or .ply, got {str(path)!r}")
+            (GIO.write_obj if suffix == ".obj" else GIO.write_ply_mesh)(path, verts, tris, normals, colors)
+        return verts, tris, normals, colors, L
+
     def get_params_for_save(self):  # gs/gaussian_splatting.py:294-311 (the five raw fields; gsgen_amd.io writes them)
         params = {k: getattr(self, k).detach() for k in self.raw_fields}
         if self.bg.type == "mlp":  # (:302: the learned background's state dict, key `mlp.params`)

@@ -792,6 +792,23 @@ int gsgen_density_grid(const float *mean, const float *qvec, const float *scale,
                        uint32_t K, uint32_t skip_nearest, float *out, void *workspace, size_t workspace_bytes,
                        gsgen_stream_t stream);
 
+/* The same field at Q points of the caller's own (mesh vertices: normals and colours), one fused search-and-sum launch, queries in
+ * the caller's order.  With the list of the Ks = K + skip_nearest nearest centres of a point q, d = q - mean_j,
+ * t_j = opacity_j * exp(-0.5 * d^T Sigma_j^-1 d) evaluated as gsgen_density_grid evaluates it:
+ *   density [Q]    sum of t_j over list entries skip_nearest .. Ks-1: bit-identical to gsgen_density_grid at the same coordinates;
+ *   grad    [Q,3]  the gradient of that sum in q with the neighbour set held fixed: sum of -(t_j * (Sigma_j^-1 d));
+ *   rgb     [Q,3]  sum of t_j color_j / sum of t_j over ALL Ks entries (the nearest centre counts even where the field drops it);
+ *                  where the denominator is below 2^-126, the colour of the nearest centre, copied.  color [N,3], any range.
+ * Any of density, grad, rgb may be NULL (not computed; the others' bits do not depend on it); rgb without color: GSGEN_EINVAL.
+ * A non-finite point writes 0 everywhere; a missing neighbour contributes nothing.  The gradient's Sigma_j^-1 is the same closed
+ * form evaluated in fp64 and rounded to fp32 once (the workspace holds it behind the lattice's layout:
+ * gsgen_density_points_workspace_bytes(N, K), for either value of skip_nearest); the terms t_j take the lattice's own record.
+ * Other argument rules and capturability as gsgen_density_grid; Q == 0: 0 (success), nothing enqueued. */
+size_t gsgen_density_points_workspace_bytes(uint32_t n_points, uint32_t K);
+int gsgen_density_points(const float *mean, const float *qvec, const float *scale, const float *opacity, const float *color,
+                         uint32_t N, const float *points, uint32_t Q, uint32_t K, uint32_t skip_nearest, float *density,
+                         float *grad, float *rgb, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
+
 /* ---- exact farthest point sampling (gsgen_amd/csrc/fps.hip) ------------------------------------------------------
  * replaces pytorch3d's sample_farthest_points as utils/ops.py:76-100 calls it (guidance/point_e.py:120-127, :169-179).
  * points fp32, n_starts clouds of [n_points, dim] rows, cloud_stride floats between the clouds of consecutive starts (0: every
