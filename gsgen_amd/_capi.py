@@ -155,6 +155,7 @@ OPTIONAL_SIGNATURES = {
     "gsgen_knn_query": [vp, u32, vp, u32, u32, vp, vp, vp, sz, vp],
     "gsgen_density_grid": [vp, vp, vp, vp, u32, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp, sz, vp],
     "gsgen_density_points": [vp, vp, vp, vp, vp, u32, vp, u32, u32, u32, vp, vp, vp, vp, sz, vp],
+    "gsgen_point_normals": [vp, u32, u32, u32, vp, vp, vp, vp, sz, vp],
     "gsgen_fps": [vp, u32, u32, sz, vp, vp, u32, u32, vp, vp, sz, i32, vp],
     "gsgen_image_loss_forward": [vp, vp, u32, u32, u32, u32, u32, f32, i32, i32, vp, vp, sz, vp],
     "gsgen_image_loss_backward": [vp, vp, u32, u32, u32, u32, u32, f32, i32, vp, vp, vp, sz, vp],
@@ -169,6 +170,7 @@ OPTIONAL_SIZE_FUNCS = {
     "gsgen_knn_query_workspace_bytes": [u32, u32, u32],
     "gsgen_density_grid_workspace_bytes": [u32, u32],
     "gsgen_density_points_workspace_bytes": [u32, u32],
+    "gsgen_point_normals_workspace_bytes": [u32, u32],
     "gsgen_fps_workspace_bytes": [u32, u32, u32, u32, i32],
     "gsgen_image_loss_workspace_bytes": [u32, u32, u32, u32, u32, i32],
     "gsgen_marching_cubes_workspace_bytes": [u32, u32, u32],

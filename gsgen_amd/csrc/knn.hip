@@ -27,7 +27,7 @@
 //      and the grid only while the box is within its K-th distance.  Every bound is shrunk by a margin that covers the rounding
 //      of the cell assignment, so pruning never drops a candidate that could enter the list.
 //
-// Steps 1-3 are the INDEX over `points` (build_index, in knn_index.hpp beside this file: fps.hip builds the same index); step 4 is one of four consumers of it:
+// Steps 1-3 are the INDEX over `points` (build_index, in knn_index.hpp beside this file: fps.hip builds the same index); step 4 is one of five consumers of it:
 //   k_knn_query       every point is a query (gsgen_knn, above).
 //   k_knn_query_ext   queries from an array of their own, in the caller's order (gsgen_knn_query): d = p_j - q.  The query's cell
 //                     comes from the index's Params; a query outside the grid box takes the outlier-query path, a non-finite
@@ -38,6 +38,8 @@
 //                     Sigma^-1 = R diag(1 / s^2) R^T in closed form, once per Gaussian (k_density_prep).
 //   k_density_points  the same search and sum at points of the caller's own, one lane per point as k_knn_query_ext, with the sum's
 //                     gradient and a density-weighted colour beside its value (gsgen_density_points: mesh vertex normals and colours).
+//   k_point_normals   the self search of k_knn_query, then the covariance of the neighbourhood and its eigen-frame from the list in
+//                     registers (gsgen_point_normals: pytorch3d's estimate_pointcloud_normals); K up to 64, a list width of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -138,17 +140,11 @@ __device__ __forceinline__ void scan_grid(unsigned long long (&list)[L], const P
 // Sorted layout: [cells 0 .. cap-1 | outliers (finite, outside the grid box) | non-finite].  A query in the grid box searches the
 // grid, then the outliers if the box's exterior is nearer than its K-th distance; an outlier query searches the outliers first,
 // then the grid with the distance to the box as a floor (a far outlier is done after the first bound).
+// The self search of the point at position t of the sorted copy (its list: `list`, padded by the caller).  A non-finite point
+// (t >= start[cap + 1]) searches nothing.
 template <int L>
-__global__ void __launch_bounds__(kBlock) k_knn_query(uint32_t N, uint32_t K, uint32_t cap, const Params *__restrict__ P,
-                                                       const uint32_t *__restrict__ start, const float4 *__restrict__ sorted,
-                                                       float *__restrict__ dist2, int32_t *__restrict__ idx) {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= N) return;
-  const float4 q = sorted[t];
-  const uint32_t qi = __float_as_uint(q.w);
-  unsigned long long list[L];
-#pragma unroll
-  for (int k = 0; k < L; ++k) list[k] = kPad;
+__device__ __forceinline__ void search_self(unsigned long long (&list)[L], uint32_t t, uint32_t cap, const Params *__restrict__ P,
+                                            const uint32_t *__restrict__ start, const float4 *__restrict__ sorted, const float4 q) {
   const uint32_t o_begin = start[cap], o_end = start[cap + 1];
   if (t < o_begin) {
     scan_grid<L>(list, P, start, sorted, q, 0.0f);
@@ -173,6 +169,20 @@ __global__ void __launch_bounds__(kBlock) k_knn_query(uint32_t N, uint32_t K, ui
     }
     scan_grid<L>(list, P, start, sorted, q, sqrtf(g2));
   }
+}
+
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_knn_query(uint32_t N, uint32_t K, uint32_t cap, const Params *__restrict__ P,
+                                                       const uint32_t *__restrict__ start, const float4 *__restrict__ sorted,
+                                                       float *__restrict__ dist2, int32_t *__restrict__ idx) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= N) return;
+  const float4 q = sorted[t];
+  const uint32_t qi = __float_as_uint(q.w);
+  unsigned long long list[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) list[k] = kPad;
+  search_self<L>(list, t, cap, P, start, sorted, q);
   float *drow = dist2 + (size_t)qi * K;
   int32_t *irow = idx + (size_t)qi * K;
 #pragma unroll
@@ -414,6 +424,198 @@ __global__ void __launch_bounds__(kBlock) k_density_points(uint32_t Q, uint32_t 
   }
 }
 
+// --- 4e. point-cloud normals ------------------------------------------------------------------------------------------------
+// pytorch3d's estimate_pointcloud_local_coord_frames (the reference's estimate_normal, utils/ops.py:62-72) fused with the self
+// search: the list of k_knn_query<L> for the same K, bit for bit, then from the list in registers (K counts the point itself):
+//   d_k = p_jk - p_i per component, list order;  m = (sum_k d_k) / K from 0.0f;  c_k = d_k - m;
+//   C_ab = (sum_k c_ka c_kb) / K for the six unique entries, list order (get_point_covariances: divided by K, not K - 1).
+// Eigen-decomposition of C: cyclic Jacobi (kJacobiSweeps sweeps over (0,1), (0,2), (1,2)) on C scaled by the power of two that
+// brings its largest diagonal entry into [1/2, 1), eigenvalues ascending (`curvature`), frame columns n (smallest), y, z (largest).
+// Every element is a named scalar: nothing is indexed at run time.
+// disambiguate != 0 (_disambiguate_vector_directions), for v = n and v = z: proj_k = (vx dx + vy dy) + vz dz, n_pos = #{proj_k > 0},
+// n_neg = #{proj_k < 0}.  2 n_pos >= K: v; else 2 n_neg >= K: -v (the point itself has proj 0, so at most one holds and the result
+// does not depend on the solver's sign).  Neither: the direction with sum_k proj_k > 0 (list order from 0.0f; the sum of -v is the
+// negation, exactly); a sum that is not positive either way: first non-zero component positive.  pytorch3d's answer there depends
+// on its solver's sign: this is the one place where the result is defined more tightly.  Then y = n x z.
+// disambiguate == 0: the solver's three columns, each with its first non-zero component positive.
+// A non-finite point and a row short of K finite neighbours write zeros.  normals / curvature / frames may be null (uniform test).
+constexpr int kJacobiSweeps = 6;
+
+// One Jacobi rotation in the (p, q) plane of the symmetric matrix (r: the third index) and of the eigenvector columns p, q.
+// t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (a_qq - a_pp) / (2 a_pq): the smaller root, |t| <= 1.  a_pq == 0, or a
+// theta whose square overflows: t = 0, nothing moves.
+__device__ __forceinline__ void jacobi_rotate(float &app, float &aqq, float &apq, float &arp, float &arq, float &v0p, float &v0q,
+                                              float &v1p, float &v1q, float &v2p, float &v2q) {
+  float t = 0.0f;
+  if (apq != 0.0f) {
+    const float theta = (aqq - app) / (2.0f * apq);
+    const float r = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
+    t = theta < 0.0f ? -r : r;
+  }
+  const float c = 1.0f / sqrtf(t * t + 1.0f), s = t * c;
+  const float h = t * apq;
+  app = app - h;
+  aqq = aqq + h;
+  apq = 0.0f;
+  const float rp = arp, rq = arq;
+  arp = c * rp - s * rq;
+  arq = s * rp + c * rq;
+  const float a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
+  v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
+  v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
+  v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
+}
+
+// (lambda_a, column a) <-> (lambda_b, column b) when lambda_a > lambda_b
+__device__ __forceinline__ void order_pair(float &la, float &lb, float &a0, float &a1, float &a2, float &b0, float &b1, float &b2) {
+  if (la > lb) {
+    float w;
+    w = la; la = lb; lb = w;
+    w = a0; a0 = b0; b0 = w;
+    w = a1; a1 = b1; b1 = w;
+    w = a2; a2 = b2; b2 = w;
+  }
+}
+
+__device__ __forceinline__ void unit3(float &x, float &y, float &z) {
+  const float n = sqrtf(x * x + y * y + z * z);
+  x = x / n; y = y / n; z = z / n;
+}
+
+// true: the first non-zero component of (x, y, z) is negative
+__device__ __forceinline__ bool first_negative(float x, float y, float z) {
+  return x != 0.0f ? x < 0.0f : (y != 0.0f ? y < 0.0f : z < 0.0f);
+}
+
+template <int L>
+__global__ void __launch_bounds__(kBlock) k_point_normals(uint32_t N, uint32_t K, uint32_t disambiguate, uint32_t cap,
+                                                           const Params *__restrict__ P, const uint32_t *__restrict__ start,
+                                                           const float4 *__restrict__ sorted, const float *__restrict__ points,
+                                                           float *__restrict__ normals, float *__restrict__ curvature,
+                                                           float *__restrict__ frames) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= N) return;
+  const float4 q = sorted[t];
+  const uint32_t qi = __float_as_uint(q.w);
+  unsigned long long list[L];
+#pragma unroll
+  for (int k = 0; k < L; ++k) list[k] = kPad;
+  search_self<L>(list, t, cap, P, start, sorted, q);
+  const float fK = (float)K;
+  // the neighbourhood's mean difference; a padded entry among the first K: a degenerate row
+  bool padded = false;
+  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    if ((uint32_t)k < K) {
+      const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+      if (j == 0xffffffffu) {
+        padded = true;
+      } else {
+        sx += points[3 * (size_t)j] - q.x;
+        sy += points[3 * (size_t)j + 1] - q.y;
+        sz += points[3 * (size_t)j + 2] - q.z;
+      }
+    }
+  }
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f, yx = 0.0f, yy = 0.0f, yz = 0.0f, zx = 0.0f, zy = 0.0f, zz = 0.0f;
+  float l0 = 0.0f, l1 = 0.0f, l2 = 0.0f;
+  if (!padded) {
+    const float mx = sx / fK, my = sy / fK, mz = sz / fK;
+    float c00 = 0.0f, c01 = 0.0f, c02 = 0.0f, c11 = 0.0f, c12 = 0.0f, c22 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+      if ((uint32_t)k < K) {
+        const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+        const float cx = (points[3 * (size_t)j] - q.x) - mx;
+        const float cy = (points[3 * (size_t)j + 1] - q.y) - my;
+        const float cz = (points[3 * (size_t)j + 2] - q.z) - mz;
+        c00 += cx * cx; c01 += cx * cy; c02 += cx * cz;
+        c11 += cy * cy; c12 += cy * cz; c22 += cz * cz;
+      }
+    }
+    c00 = c00 / fK; c01 = c01 / fK; c02 = c02 / fK;
+    c11 = c11 / fK; c12 = c12 / fK; c22 = c22 / fK;
+    // scale by a power of two (exact): the largest diagonal entry, which bounds every entry of a covariance, into [1/2, 1)
+    const float big = fmaxf(c00, fmaxf(c11, c22));
+    int e = 0;
+    if (big > 0.0f && big <= 3.402823466e38f) (void)frexpf(big, &e);
+    float a00 = ldexpf(c00, -e), a01 = ldexpf(c01, -e), a02 = ldexpf(c02, -e);
+    float a11 = ldexpf(c11, -e), a12 = ldexpf(c12, -e), a22 = ldexpf(c22, -e);
+    float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+      jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0, 1), r = 2
+      jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0, 2), r = 1
+      jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1, 2), r = 0
+    }
+    // ascending: columns (v00, v10, v20), (v01, v11, v21), (v02, v12, v22) follow their eigenvalues
+    order_pair(a00, a11, v00, v10, v20, v01, v11, v21);
+    order_pair(a11, a22, v01, v11, v21, v02, v12, v22);
+    order_pair(a00, a11, v00, v10, v20, v01, v11, v21);
+    l0 = ldexpf(a00, e); l1 = ldexpf(a11, e); l2 = ldexpf(a22, e);
+    nx = v00; ny = v10; nz = v20;
+    yx = v01; yy = v11; yz = v21;
+    zx = v02; zy = v12; zz = v22;
+    unit3(nx, ny, nz);
+    unit3(zx, zy, zz);
+    if (disambiguate != 0) {
+      uint32_t n_pos = 0, n_neg = 0, z_pos = 0, z_neg = 0;
+      float n_sum = 0.0f, z_sum = 0.0f;
+#pragma unroll
+      for (int k = 0; k < L; ++k) {
+        if ((uint32_t)k < K) {
+          const uint32_t j = (uint32_t)(list[k] & 0xffffffffull);
+          const float dx = points[3 * (size_t)j] - q.x, dy = points[3 * (size_t)j + 1] - q.y, dz = points[3 * (size_t)j + 2] - q.z;
+          const float pn = nx * dx + ny * dy + nz * dz;
+          const float pz = zx * dx + zy * dy + zz * dz;
+          n_pos += pn > 0.0f ? 1u : 0u; n_neg += pn < 0.0f ? 1u : 0u; n_sum += pn;
+          z_pos += pz > 0.0f ? 1u : 0u; z_neg += pz < 0.0f ? 1u : 0u; z_sum += pz;
+        }
+      }
+      bool flip_n, flip_z;
+      if (2u * n_pos >= K) flip_n = false;
+      else if (2u * n_neg >= K) flip_n = true;
+      else if (n_sum > 0.0f) flip_n = false;
+      else if (n_sum < 0.0f) flip_n = true;
+      else flip_n = first_negative(nx, ny, nz);
+      if (2u * z_pos >= K) flip_z = false;
+      else if (2u * z_neg >= K) flip_z = true;
+      else if (z_sum > 0.0f) flip_z = false;
+      else if (z_sum < 0.0f) flip_z = true;
+      else flip_z = first_negative(zx, zy, zz);
+      if (flip_n) { nx = -nx; ny = -ny; nz = -nz; }
+      if (flip_z) { zx = -zx; zy = -zy; zz = -zz; }
+      yx = ny * zz - nz * zy;
+      yy = nz * zx - nx * zz;
+      yz = nx * zy - ny * zx;
+    } else {
+      unit3(yx, yy, yz);
+      if (first_negative(nx, ny, nz)) { nx = -nx; ny = -ny; nz = -nz; }
+      if (first_negative(yx, yy, yz)) { yx = -yx; yy = -yy; yz = -yz; }
+      if (first_negative(zx, zy, zz)) { zx = -zx; zy = -zy; zz = -zz; }
+    }
+  }
+  if (normals != nullptr) {
+    normals[3 * (size_t)qi] = nx; normals[3 * (size_t)qi + 1] = ny; normals[3 * (size_t)qi + 2] = nz;
+  }
+  if (curvature != nullptr) {
+    curvature[3 * (size_t)qi] = l0; curvature[3 * (size_t)qi + 1] = l1; curvature[3 * (size_t)qi + 2] = l2;
+  }
+  if (frames != nullptr) {
+    float *f = frames + 9 * (size_t)qi;
+    f[0] = nx; f[1] = yx; f[2] = zx;
+    f[3] = ny; f[4] = yy; f[5] = zy;
+    f[6] = nz; f[7] = yz; f[8] = zz;
+  }
+}
+
+template <int L>
+inline void launch_point_normals(uint32_t N, uint32_t K, uint32_t disambiguate, uint32_t cap, const Ws &w, const float *points,
+                                 float *normals, float *curvature, float *frames, hipStream_t s) {
+  hipLaunchKernelGGL((k_point_normals<L>), dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, K, disambiguate, cap,
+                     (const Params *)w.P, (const uint32_t *)w.start, (const float4 *)w.sorted, points, normals, curvature, frames);
+}
+
 template <int L>
 inline void launch_query(uint32_t N, uint32_t K, uint32_t cap, const Ws &w, float *dist2, int32_t *idx, hipStream_t s) {
   hipLaunchKernelGGL((k_knn_query<L>), dim3((N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, K, cap, (const Params *)w.P,
@@ -501,6 +703,30 @@ int gsgen_knn_query(const float *points, uint32_t n_points, const float *queries
   else if (K <= 8) launch_query_ext<8>(Q, K, cap, w, queries, dist2, idx, s);
   else if (K <= 16) launch_query_ext<16>(Q, K, cap, w, queries, dist2, idx, s);
   else launch_query_ext<32>(Q, K, cap, w, queries, dist2, idx, s);
+  return (int)hipGetLastError();
+}
+
+size_t gsgen_point_normals_workspace_bytes(uint32_t n_points, uint32_t K) {
+  if (n_points == 0 || K < 3 || K > 64) return 0;
+  return carve(nullptr, n_points, K).bytes;
+}
+
+int gsgen_point_normals(const float *points, uint32_t n_points, uint32_t K, uint32_t disambiguate, float *normals, float *curvature,
+                        float *frames, void *workspace, size_t workspace_bytes, gsgen_stream_t stream) {
+  if (K < 3 || K > 64) return GSGEN_EUNSUPPORTED;
+  if (n_points == 0 || K >= n_points || n_points > 0x7fffffffu) return GSGEN_EINVAL;
+  if (!points || !workspace || (!normals && !curvature && !frames)) return GSGEN_EINVAL;
+  const uint32_t N = n_points;
+  const Ws w = carve(workspace, N, K);
+  if (w.bytes > workspace_bytes) return GSGEN_EWORKSPACE;
+  const uint32_t cap = cell_cap(N, K);
+  hipStream_t s = (hipStream_t)stream;
+  if (int e = build_index(points, N, K, w, s)) return e;
+  if (K <= 4) launch_point_normals<4>(N, K, disambiguate, cap, w, points, normals, curvature, frames, s);
+  else if (K <= 8) launch_point_normals<8>(N, K, disambiguate, cap, w, points, normals, curvature, frames, s);
+  else if (K <= 16) launch_point_normals<16>(N, K, disambiguate, cap, w, points, normals, curvature, frames, s);
+  else if (K <= 32) launch_point_normals<32>(N, K, disambiguate, cap, w, points, normals, curvature, frames, s);
+  else launch_point_normals<64>(N, K, disambiguate, cap, w, points, normals, curvature, frames, s);  // (the one 64-entry list)
   return (int)hipGetLastError();
 }
 

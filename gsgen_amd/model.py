@@ -20,8 +20,11 @@ optimizer / update / densify / prune / log / auxiliary_loss / bg(rays_d) exist s
 drop-in (gsgen_amd.install_as_gs) stays available for code that calls the 23 names directly, at the reference's serial shape
 (bench.py reports both: `dropin_gs_surface` against `model_surface`).
 
-What is NOT carried over (raises NotImplementedError when configured or called): normal_as_rgb, pbr / specular shading, overrides of
-anything but `color`, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of update().  The learned
+What is NOT carried over (raises NotImplementedError when configured or called): pbr / specular shading (with normal_type "learned"),
+overrides of anything but `color`, the pbr-only penalties (specular, normal) and `move`, the gradient-mask windows of update().
+cfg.normal_as_rgb (conf/renderer/normal_as_rgb.yaml) renders: forward(batch) estimates the centres' normals (update_normal(), on
+gsgen_amd.normals: pytorch3d's estimate_pointcloud_normals as one HIP launch, no autograd graph), renders them as the colour
+override (normal + 1) / 2 and normalises every pixel (gs/gaussian_splatting.py:1424-1427, :1463-1464).  The learned
 MLPBackground (background.type "mlp", tinycudann in the reference) runs on gsgen_amd.background.  Penalty losses and compatness densification take their neighbours from gsgen_amd.knn (the HIP kNN kernel).
 The densify / prune policies themselves live in gsgen_amd.densify (this class delegates; AdaptiveControl is the multi-rank form on a
 FusedAdam), the flat-buffer optimiser in gsgen_amd.optim.
@@ -225,9 +228,11 @@ class GaussianSplattingRenderer(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.device = torch.device(_get(cfg, "device", "cuda"))
-        for k in ("pbr", "normal_as_rgb"):
-            if _get(cfg, k, False):
-                raise NotImplementedError(f"gsgen_amd.model: cfg.{k} is outside the rasterizer path this library replaces")
+        if _get(cfg, "pbr", False):
+            raise NotImplementedError("gsgen_amd.model: cfg.pbr is outside the rasterizer path this library replaces")
+        self.normal_as_rgb = bool(_get(cfg, "normal_as_rgb", False))
+        self.normal_type = _get(cfg, "normal_type", "estimated")  # gs/gaussian_splatting.py:75
+        self._normal = None
         self._act_names = tuple(_get(cfg, k) for k in ("svec_act", "alpha_act", "color_act"))
         self.svec_act, self.alpha_act, self.color_act = (activations[_get(cfg, k)] for k in ("svec_act", "alpha_act", "color_act"))
         self.svec_inv_act, self.alpha_inv_act, self.color_inv_act = (
@@ -345,8 +350,35 @@ class GaussianSplattingRenderer(nn.Module):
         """batch: {"c2w": [B, 3|4, 4] tensor (any device) or array, "camera_info": B CameraInfo-like objects (fx, fy, cx, cy, w, h,
         near_plane, far_plane: the reference's utils/camera.py:219-259 or gsgen_amd.renderer.CameraInfo)}.
         -> {"rgb": [B,H,W,3]} + {"depth", "opacity", "z_var": [B,H,W,1]} unless rgb_only (gs/gaussian_splatting.py:1423-1466).
-        use_bg is accepted and ignored, as in the reference (:1324-1327: the background is always composited)."""
-        return self._render(batch, use_bg, rgb_only)
+        use_bg is accepted and ignored, as in the reference (:1324-1327: the background is always composited).
+        With cfg.normal_as_rgb (:1424-1427, :1463-1464) the estimated normals are rendered in place of the colours, as
+        (normal + 1) / 2, and every pixel is normalised afterwards: the view that shows the geometry a run has learnt.  The override
+        is a constant; gradients reach mean / qvec / svec / alpha through the compositing."""
+        if not self.normal_as_rgb:
+            return self._render(batch, use_bg, rgb_only)
+        out = self._render(batch, use_bg, rgb_only, color=(self.update_normal() + 1.0) * 0.5)
+        out["rgb"] = (torch.nn.functional.normalize(out["rgb"], dim=-1, eps=1e-6) + 1.0) / 2.0
+        return out
+
+    # ---- normals (gs/gaussian_splatting.py:1186-1196) -------------------------------------------------------------------
+    def _estimate_normal(self):
+        if self.normal_type != "estimated":
+            if self.normal_type == "learned":
+                raise NotImplementedError("gsgen_amd.model: normal_type 'learned' belongs to pbr shading, which this class does not implement")
+            raise ValueError(f"Unknown normal type: {self.normal_type}")
+        from .normals import estimate_normal
+        return estimate_normal(self.mean, **(_to_plain(_get(self.cfg, "normal")) or {}))
+
+    def update_normal(self):
+        """estimates the normals of the current centres with cfg.normal (neighborhood_size, disambiguate_directions) and keeps them
+        for the render -> [N,3], no autograd graph (gsgen_amd.normals)"""
+        self._normal = self._estimate_normal()
+        return self._normal
+
+    @property
+    def normal(self):
+        """the normals of the current centres, estimated at every read as the reference's property does"""
+        return self._estimate_normal()
 
     def _render(self, batch, use_bg=True, rgb_only=False, color=None):
         """forward's render; color: [N,3] activated colours in place of the model's (render_one's overrides)"""

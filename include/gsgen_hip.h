@@ -809,6 +809,25 @@ int gsgen_density_points(const float *mean, const float *qvec, const float *scal
                          uint32_t N, const float *points, uint32_t Q, uint32_t K, uint32_t skip_nearest, float *density,
                          float *grad, float *rgb, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
 
+/* Point-cloud normals and local frames (pytorch3d's estimate_pointcloud_local_coord_frames, as utils/ops.py:62-72 calls it), fused
+ * with the self search: the neighbourhood of point i is row i of gsgen_knn for the same K (the point itself included), never written
+ * to memory.  In fp32, in this order: d_k = p_jk - p_i; m = (sum_k d_k) / K; c_k = d_k - m; C = (sum_k c_k c_k^T) / K; the eigen-
+ * decomposition of C by cyclic Jacobi, eigenvalues ascending.
+ *   normals   [n_points,3]    the unit eigenvector of the smallest eigenvalue;
+ *   curvature [n_points,3]    the eigenvalues, ascending;
+ *   frames    [n_points,3,3]  row-major, columns n, y, z (z: the largest eigenvalue): frames[i][r][0] == normals[i][r].
+ * disambiguate != 0: n and z point to the side where at least K/2 of the neighbours lie (pytorch3d's rule); where neither side
+ * reaches K/2, to the side of the positive sum of projections, and failing that the first non-zero component is positive (pytorch3d's
+ * result depends on its solver's sign there); y = n x z.  disambiguate == 0: the solver's columns, each with its first non-zero
+ * component positive.  A non-finite point and a row short of K finite neighbours write zeros; a rank-deficient covariance still
+ * writes a unit normal and an orthonormal frame, the same bits on every run.  Any of the three outputs may be NULL (not written;
+ * the others' bits do not depend on it); all three NULL: GSGEN_EINVAL.  K in 3..64 (else GSGEN_EUNSUPPORTED, workspace size 0);
+ * n_points == 0, K >= n_points (pytorch3d requires a cloud larger than the neighbourhood) or a null points / workspace:
+ * GSGEN_EINVAL; a short workspace: GSGEN_EWORKSPACE.  Capturable like gsgen_knn. */
+size_t gsgen_point_normals_workspace_bytes(uint32_t n_points, uint32_t K);
+int gsgen_point_normals(const float *points, uint32_t n_points, uint32_t K, uint32_t disambiguate, float *normals, float *curvature,
+                        float *frames, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
+
 /* ---- exact farthest point sampling (gsgen_amd/csrc/fps.hip) ------------------------------------------------------
  * replaces pytorch3d's sample_farthest_points as utils/ops.py:76-100 calls it (guidance/point_e.py:120-127, :169-179).
  * points fp32, n_starts clouds of [n_points, dim] rows, cloud_stride floats between the clouds of consecutive starts (0: every
