@@ -15,6 +15,8 @@
                          mlp_background_images, mlp_background_over)
     gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt), with vertex
                          normals and colours from the same field (vertex_attributes, colored_density_mesh, colored_mesh_from_ckpt)
+    gsgen_amd.mesh_sample  a triangle mesh to an evenly spaced point cloud on the GPU, trimesh's call shapes (mesh_area, sample_surface,
+                         remove_close, sample_surface_even), and the reference's mesh initialisation on it (load_mesh_as_pcd, mesh_initialize)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
 There is no CPU implementation in this package: every entry point needs the HIP library and
@@ -42,6 +44,12 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
                 "colored_mesh_from_ckpt"):
         from . import mesh
         return getattr(mesh, name)
+    if name == "mesh_sample":
+        import importlib
+        return importlib.import_module(".mesh_sample", __name__)
+    if name in ("mesh_area", "sample_surface", "remove_close", "sample_surface_even", "load_mesh_as_pcd", "mesh_initialize"):
+        from . import mesh_sample
+        return getattr(mesh_sample, name)
     raise AttributeError(name)
 
 

@@ -954,6 +954,41 @@ int gsgen_mlp_background_backward(const float *params, const void *cams, size_t 
                                   uint32_t H, uint32_t W, const float *opacity, const float *grad_out, float *grad_params,
                                   float *grad_opacity, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
 
+/* ---- triangle mesh -> evenly spaced point cloud (gsgen_amd/csrc/mesh_sample.hip) ------------------------------------------
+ * replaces trimesh's sample_surface / remove_close / sample_surface_even under utils/mesh.py:52-69.  DESIGN.md ("Mesh sampling")
+ * has the definitions.
+ * gsgen_mesh_sample: verts [V][3] float, tris [F][3] int32, uniforms [M][3] float in [0, 1) = (u_face, r1, r2), all on the device.
+ *   Face weight = 0.5 |(v1 - v0) x (v2 - v0)| in fp64; 0 for a zero area, a non-finite vertex or a vertex index outside [0, V).
+ *   Sample m takes the first face i with cum[i] >= (double)u_face * total and weight > 0 (cum: the inclusive fp64 scan of the
+ *   weights), flips (r1, r2) to (1 - r1, 1 - r2) where r1 + r2 > 1, and writes, each where the pointer is not NULL:
+ *   points [M][3] = v0 + ((v1 - v0) r1 + (v2 - v0) r2), face_index [M], barycentric [M][2] = (r1, r2) after the flip, attr_out
+ *   [M][A] from attributes [V][A] in the same form (A in 1..8; A = 0 with attributes = attr_out = NULL), normals [M][3] = the
+ *   face's unit normal.  status (optional, 8-byte aligned, 16 bytes): uint32 bad_faces (faces with an index out of range),
+ *   uint32 zero_area_flag, double total area.  Total area 0: every output row is NaN, face_index -1, zero_area_flag 1.
+ *   A above 8, attributes without A or the reverse, a misaligned status, a null tris / workspace / verts / uniforms that is
+ *   needed: GSGEN_EINVAL; a short workspace: GSGEN_EWORKSPACE.  F == 0, or M == 0 without a status block: 0, nothing enqueued;
+ *   M == 0 with one: the weights and the scan alone (how the area is read).  The workspace (8 bytes per face and a little) may
+ *   be dirty and unaligned.
+ * gsgen_remove_close_init / _rounds: points [N][3]; keep [N] bytes.  Point i is kept iff no kept j < i has
+ *   (dx dx + dy dy) + dz dz <= r r in fp32; a non-finite point is removed and is nobody's neighbour.  init builds the grid, sorts
+ *   the points by cell and resets the state and keep[] (all 0); rounds enqueues n_rounds decision rounds (one launch each; keep[i]
+ *   becomes 1 when i is decided kept) and then writes the number of points the last of them left undecided to *remaining
+ *   (optional; n_rounds = 0: the count as it stands); a round that finds nothing undecided returns at once.  The same N, radius,
+ *   keep and workspace go to init and to every rounds call after it; keep[] is final once *remaining is 0.  radius < 0 or NaN:
+ *   GSGEN_EINVAL; a short workspace: GSGEN_EWORKSPACE; N == 0: 0, nothing enqueued.  The workspace (about 33 bytes per point) may
+ *   start at any alignment.
+ * Nothing here allocates or synchronises with the host; launch shapes depend on the sizes alone. */
+size_t gsgen_mesh_sample_workspace_bytes(uint32_t n_faces);
+int gsgen_mesh_sample(const float *verts, uint32_t n_verts, const int32_t *tris, uint32_t n_faces, const float *uniforms,
+                      uint32_t n_samples, const float *attributes, uint32_t n_attr, float *points, int32_t *face_index,
+                      float *barycentric, float *attr_out, float *normals, void *status, void *workspace, size_t workspace_bytes,
+                      gsgen_stream_t stream);
+size_t gsgen_remove_close_workspace_bytes(uint32_t n_points);
+int gsgen_remove_close_init(const float *points, uint32_t n_points, float radius, uint8_t *keep, void *workspace,
+                            size_t workspace_bytes, gsgen_stream_t stream);
+int gsgen_remove_close_rounds(uint32_t n_rounds, uint32_t n_points, float radius, uint8_t *keep, uint32_t *remaining, void *workspace,
+                              size_t workspace_bytes, gsgen_stream_t stream);
+
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
  * lane owns (-1: duplicate holder); P in {8,16,32,64}. */
