@@ -77,10 +77,11 @@ __device__ __forceinline__ void stage_batch(Stage<MODE, CB, KB, WITH_COL> &S, co
       mx = m.x; my = m.y;
       const float al_in = p.alpha[id];
       // RGB / scalar / RGB + heads: a record with a non-finite mean or opacity never contributes.  a = 0 alone does not see to
-      // that: 0 * G is NaN for the G of a non-finite offset, and !(NaN < 1/255) takes the entry; and fminf(NaN, 0.99) is 0.99,
-      // a near-opaque layer.  Such a record is staged with a = 0, a zero factor AND a zero mean (G = 1, a G = 0: skipped).
+      // that: 0 * G is NaN for the G of a non-finite offset, and !(NaN < 1/255) takes the entry; and fminf(NaN, 0.99) and
+      // fminf(+inf, 0.99) are 0.99, a near-opaque layer.  Such a record is staged with a = 0, a zero factor AND a zero mean
+      // (G = 1, a G = 0: skipped).  SH: prep_record repairs the record itself (mean, covariance and 1 / det are all staged).
       bool live = true;
-      if constexpr (MODE != MODE_SH) live = finite_f(mx) && finite_f(my) && (al_in == al_in);
+      if constexpr (MODE != MODE_SH) live = finite_f(mx) && finite_f(my) && finite_f(al_in);
       if (prepared) {
         // the record the projection launch prepared for this (view, Gaussian) (gsgen_geometry_view::chol): no fp64 chain here
         const float4 q = *reinterpret_cast<const float4 *>(p.chol + 4 * (size_t)id);
@@ -91,7 +92,12 @@ __device__ __forceinline__ void stage_batch(Stage<MODE, CB, KB, WITH_COL> &S, co
         const float4 c = *reinterpret_cast<const float4 *>(p.cov + 4 * (size_t)id);
         c0 = c.x; c1 = c.y; c2 = c.z; c3 = c.w;
         const GRec r = prep_record<MODE>(mx, my, c0, c1, c2, c3, al_in);
-        a = live ? r.a : 0.0f; p0 = live ? r.p0 : 0.0f; p1 = live ? r.p1 : 0.0f; p2 = live ? r.p2 : 0.0f;
+        if constexpr (MODE == MODE_SH) {
+          mx = r.mx; my = r.my; c0 = r.c0; c1 = r.c1; c2 = r.c2; c3 = r.c3;
+          a = r.a; p0 = r.p0; p1 = r.p1; p2 = r.p2;
+        } else {
+          a = live ? r.a : 0.0f; p0 = live ? r.p0 : 0.0f; p1 = live ? r.p1 : 0.0f; p2 = live ? r.p2 : 0.0f;
+        }
       }
       if (!live) { mx = 0.0f; my = 0.0f; }
     }

@@ -260,16 +260,17 @@ struct GRec {
 // RGB/scalar: p0..p2 = Cholesky factor of the quadratic form scaled so that
 // G = exp2(-(u^2+v^2)), u = p0 x + p1 y, v = p2 y (computed in fp64 once per record).
 // SH: p0 = -0.5 log2(e)/det, p1 = 1/det with the fp32 determinant of kernels.h:179.
-// A degenerate / non-finite record gets a = 0 and never contributes.
+// A degenerate / non-finite record gets a = 0 and never contributes (SH: and a zero mean and the identity covariance, see below).
 template <int MODE>
 __device__ __forceinline__ GRec prep_record(float mx, float my, float c0, float c1, float c2, float c3,
                                             float alpha) {
   GRec r;
   r.mx = mx; r.my = my; r.c0 = c0; r.c1 = c1; r.c2 = c2; r.c3 = c3;
   r.p0 = 0.f; r.p1 = 0.f; r.p2 = 0.f;
-  float a = fminf(alpha, kAlphaClamp);
+  // the RAW opacity is tested: fminf(NaN, 0.99) and fminf(+inf, 0.99) are 0.99, a near-opaque layer that passes finite_f
+  const float a = fminf(alpha, kAlphaClamp);
   bool ok = finite_f(mx) && finite_f(my) && finite_f(c0) && finite_f(c1) && finite_f(c2) && finite_f(c3) &&
-            finite_f(a);
+            finite_f(alpha);
   if constexpr (MODE == MODE_SH) {
     float det;
     {
@@ -280,6 +281,10 @@ __device__ __forceinline__ GRec prep_record(float mx, float my, float c0, float 
     const float inv = 1.0f / (ok ? det : 1.0f);
     r.p0 = -0.5f * kLog2e * inv;
     r.p1 = inv;
+    // The SH kernels evaluate G from the staged mean and covariance, and a = 0 alone does not keep a bad record out: 0 * G is NaN
+    // for the G of a non-finite offset or covariance, and !(NaN < 1/255) takes the entry.  Such a record is staged as a zero
+    // mean with the identity covariance: G is finite at every pixel, a G = 0, skipped -- at no cost in the entry loops.
+    if (!ok) { r.mx = 0.f; r.my = 0.f; r.c0 = 1.f; r.c1 = 0.f; r.c2 = 0.f; r.c3 = 1.f; }
   } else {
     const CholRec c = chol_prep(c0, c1, c2, c3);  // (common.hpp: the same bits wherever it is formed)
     ok = ok && c.ok;

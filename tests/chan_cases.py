@@ -297,7 +297,7 @@ def oracle_chain(case):
         ids = np.asarray([i for lst in lists for i in lst] + [0], np.int32)
         lens = np.asarray([len(lst) for lst in lists]); en = np.cumsum(lens).astype(np.int32)
         st = np.where(lens > 0, en - lens, -1).astype(np.int32)
-        m2 = np.nan_to_num(view["m2"], nan=0.0, posinf=0.0, neginf=0.0); c2 = view["c2"].reshape(N, 2, 2); al = np.nan_to_num(a["alpha"], nan=0.0)
+        m2 = np.nan_to_num(view["m2"], nan=0.0, posinf=0.0, neginf=0.0); c2 = view["c2"].reshape(N, 2, 2); al = np.nan_to_num(a["alpha"], nan=0.0, posinf=0.0, neginf=0.0)
         geo = (view["tlp"], view["ps"][0], view["ps"][1], H, W)
         img, T = O.render_rgb_fwd(m2, c2, a["color"], al, st, en, ids, *geo)
         final = (img + T.reshape(H, W, 1) * view["bg"]).astype(np.float32)
@@ -430,10 +430,13 @@ def case_bad_records():
                     indefinite=S.add(at(24.3, 27.6), [NON_PSD * s for s in s2], 0.5),
                     nan_mean=S.add([(nan, m[1]) for m in at(22.3, 22.6)], good, 0.5),
                     inf_mean=S.add([(m[0], inf) for m in at(22.3, 22.6)], good, 0.5),
-                    nan_alpha=S.add(at(26.3, 25.6), good, nan))
+                    nan_alpha=S.add(at(26.3, 25.6), good, nan),
+                    inf_alpha=S.add(at(21.3, 26.6), good, inf),          # fminf(+inf, 0.99) is 0.99 too: the RAW opacity is tested
+                    neg_inf_alpha=S.add(at(28.3, 23.6), good, -inf))
         one = S.add(at(23.3, 24.6), good, 1.0)           # alpha = 1.0: clamped to 0.99, an ordinary record
         S.bad = list(recs.values()); S.zero = list(recs.values()); S.note.update(recs, one=one)
-        order = [recs["det_zero"], recs["nan_mean"], one, recs["indefinite"], recs["inf_mean"], recs["det_negative"], recs["nan_alpha"]]
+        order = [recs["det_zero"], recs["nan_mean"], one, recs["indefinite"], recs["inf_mean"], recs["det_negative"], recs["nan_alpha"],
+                 recs["inf_alpha"], recs["neg_inf_alpha"]]
         S.front(MID, S.thin(MID, 3) + order)
         return S
 
@@ -446,7 +449,7 @@ def case_bad_records():
                 same = np.delete(formula["take"][v][t] == ref["take"][v][t], k if t == MID else [], 1)
                 reached = formula["take"][v][t][:, k] if t == MID else np.zeros(len(same), bool)
                 assert same[~reached].all()
-            for name in ("det_zero", "det_negative", "nan_mean", "inf_mean", "nan_alpha"):
+            for name in ("det_zero", "det_negative", "nan_mean", "inf_mean", "nan_alpha", "inf_alpha", "neg_inf_alpha"):
                 assert not formula["take"][v][MID][:, S.lists[v][MID].index(S.note[name])].any()
             assert ref["take"][v][MID][:, S.lists[v][MID].index(S.note["one"])].any()
     return make, check

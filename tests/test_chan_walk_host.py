@@ -6,7 +6,7 @@ tests/test_gpu_chan_walk.py.
 
 Worst ratio of scenes.per_gaussian_grad_error(rtol 1e-3, atol 1e-5) over every tensor and launch form, CPU host build (<= 1
 passes): len_1 .. len_200 0.004 .. 0.031 (corner tile 0.002 .. 0.029), sat_last_of_batch 0.156, sat_first_of_next 0.086,
-sat_in_first_batch 0.154, sat_partial 0.067, unseen_batch 0.016, guard_trip 0.002, bad_records 0.004, empty_tiles 0.002,
+sat_in_first_batch 0.154, sat_partial 0.067, unseen_batch 0.016, guard_trip 0.002, bad_records 0.008, empty_tiles 0.002,
 clamp_straddle 0.037; the oracle's fp32 chain on the same lists: 0.018 at most.  behind_opaque: 2.79 (the alpha gradient of the
 near-opaque layers, moment form with z_var; the oracle's chain 0.010) -- held instead to |got - ref| <= 1e-3 max |ref| + FUZZ_ATOL
 per tensor, of which it uses 0.062 ("The single suffix behind near-opaque layers")."""
