@@ -17,6 +17,8 @@
                          normals and colours from the same field (vertex_attributes, colored_density_mesh, colored_mesh_from_ckpt)
     gsgen_amd.mesh_sample  a triangle mesh to an evenly spaced point cloud on the GPU, trimesh's call shapes (mesh_area, sample_surface,
                          remove_close, sample_surface_even), and the reference's mesh initialisation on it (load_mesh_as_pcd, mesh_initialize)
+    gsgen_amd.guidance   the seam between the rendered batch and the diffusion guidance: the fused resize + affine + fp16 cast of the
+                         guidance's input (to_guidance, vae_input, if_input, rgb_as_latents, resize) and the SDS loss (sds_loss)
     gsgen_amd.build      hipcc build of gsgen_amd/lib/libgsgen_hip.so (C ABI: include/gsgen_hip.h)
 
 There is no CPU implementation in this package: every entry point needs the HIP library and
@@ -50,6 +52,12 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name in ("mesh_area", "sample_surface", "remove_close", "sample_surface_even", "load_mesh_as_pcd", "mesh_initialize"):
         from . import mesh_sample
         return getattr(mesh_sample, name)
+    if name == "guidance":
+        import importlib
+        return importlib.import_module(".guidance", __name__)
+    if name in ("to_guidance", "vae_input", "if_input", "rgb_as_latents", "sds_loss"):
+        from . import guidance
+        return getattr(guidance, name)
     raise AttributeError(name)
 
 

@@ -989,6 +989,43 @@ int gsgen_remove_close_init(const float *points, uint32_t n_points, float radius
 int gsgen_remove_close_rounds(uint32_t n_rounds, uint32_t n_points, float radius, uint8_t *keep, uint32_t *remaining, void *workspace,
                               size_t workspace_bytes, gsgen_stream_t stream);
 
+/* ---- guidance seam: the guidance's input image and the SDS loss (gsgen_amd/csrc/guidance_seam.hip) ---------------------------
+ * replaces the torch sequences between the rendered batch and the diffusion guidance (guidance/stable_diffusion.py:274-312 and
+ * its siblings).  DESIGN.md ("Guidance seam") has the definitions.
+ * Guidance input: x device fp32 [B][H][W][C] channels last, C in {1, 3} -> out = scale * bilinear(x) + shift at OH x OW, torch's
+ *   upsample_bilinear2d map with align_corners=False and no antialiasing in fp32, the affine applied once after the interpolation.
+ *   out is planar [B][C][OH][OW] (out_planar != 0) or channels last [B][OH][OW][C], fp16 rounded to nearest even (out_half != 0) or
+ *   fp32; with C == 1 the two layouts are one.
+ *   The workspace holds the per-axis tables of the (H, W, OH, OW) quadruple: (i0, l1) per output index, [o_begin, o_end) per input
+ *   index.  forward with build_tables != 0 writes them first (one tiny launch; the workspace may arrive dirty and unaligned); with
+ *   build_tables == 0 it reads what an earlier forward with the same sizes and the same workspace address wrote, so a caller may
+ *   keep one workspace per quadruple.  backward always reads them: call it with the workspace a forward filled.
+ *   backward: grad_out in the layout grad_planar names, fp16 (grad_half != 0) or fp32 -> grad_x [B][H][W][C] fp32, overwritten: a
+ *   gather, one lane per input pixel, summed output row ascending then output column ascending in fp32 with the forward's own
+ *   weights (its exact adjoint); an input pixel no output read is written as an exact zero.  No float atomics, no fill.
+ * SDS loss: grad device fp32 [B][n] -> g' = clamp(nan_to_num(grad), -clip, clip) (NaN -> 0, +-Inf -> +-FLT_MAX; the clamp only with
+ *   use_clip != 0).  forward: loss_out device float[2 + B] = {0.5 sum g'^2 / B, sqrt(sum g'^2), 0.5 sum_b g'^2 per image}, sums in
+ *   fp64 in a fixed order, and g' / B saved in the workspace.  The value does not depend on latents, so they are not passed.
+ *   backward: grad_latents [B][n] = *grad_scale_dev * g' / B from the workspace the forward filled; the upstream scalar is read on
+ *   the device.  Two launches forward, one backward.
+ * A zero size or a null pointer (or a negative or NaN clip with use_clip): GSGEN_EINVAL; C not in {1, 3}, an image side above
+ * 65536, B > 65535 (SDS) or a launch grid past 2^31 - 1 workgroups: GSGEN_EUNSUPPORTED (the workspace queries answer 0 for
+ * both); a workspace smaller than the query's answer: GSGEN_EWORKSPACE; a refused call enqueues nothing.  No allocation, no host
+ * synchronisation, launch shapes from the sizes alone: capturable, and a replay sees the values then in the buffers.  Everything
+ * is bit-identical from run to run. */
+size_t gsgen_guidance_input_workspace_bytes(uint32_t H, uint32_t W, uint32_t OH, uint32_t OW);
+int gsgen_guidance_input_forward(const float *x, uint32_t B, uint32_t H, uint32_t W, uint32_t C, uint32_t OH, uint32_t OW, float scale,
+                                 float shift, int out_half, int out_planar, void *out, int build_tables, void *workspace,
+                                 size_t workspace_bytes, gsgen_stream_t stream);
+int gsgen_guidance_input_backward(const void *grad_out, int grad_half, int grad_planar, uint32_t B, uint32_t H, uint32_t W, uint32_t C,
+                                  uint32_t OH, uint32_t OW, float scale, float *grad_x, void *workspace, size_t workspace_bytes,
+                                  gsgen_stream_t stream);
+size_t gsgen_sds_loss_workspace_bytes(uint32_t B, uint32_t n);
+int gsgen_sds_loss_forward(const float *grad, uint32_t B, uint32_t n, int use_clip, float clip, float *loss_out, void *workspace,
+                           size_t workspace_bytes, gsgen_stream_t stream);
+int gsgen_sds_loss_backward(uint32_t B, uint32_t n, const float *grad_scale_dev, float *grad_latents, void *workspace,
+                            size_t workspace_bytes, gsgen_stream_t stream);
+
 /* Self test of the wave64 cross-lane reduce-scatter used by the backward (tests only):
  * in [64 lanes, P components]; out[0..64) = per-lane result, out[64..128) = the component index that
  * lane owns (-1: duplicate holder); P in {8,16,32,64}. */
