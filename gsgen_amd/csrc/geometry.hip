@@ -279,7 +279,7 @@ __device__ __forceinline__ CholK chol_k_of(const float *__restrict__ cov2d_n) {
 __device__ __forceinline__ ProjGrad project_bwd_one(uint32_t n, const float *__restrict__ mean,
                                                     const float *__restrict__ qvec, const float *__restrict__ svec,
                                                     const float *__restrict__ c2w, int detach_depth,
-                                                    double gm0, double gm1, const double (&gc)[4], float g_depth_n) {
+                                                    double gm0, double gm1, const double (&gc)[4], double g_depth_n) {
   // (fp64 throughout, fused multiply-adds allowed: the launch is bound by its fp64 issue -- 42 us per 8 x 100 k (view, Gaussian) chains
   // on MI355X with every product and sum a separate instruction and nine divisions; the exact zeros of J are left out, the two
   // normalisations multiply by one reciprocal each)
@@ -362,7 +362,7 @@ __device__ __forceinline__ ProjGrad project_bwd_one(uint32_t n, const float *__r
   const double dot = qh[0] * dq[0] + qh[1] * dq[1] + qh[2] * dq[2] + qh[3] * dq[3];
 #pragma unroll
   for (int k = 0; k < 4; ++k) o.gq[k] = (float)((dq[k] - qh[k] * dot) * inq);
-  double du[3] = {gm0 * iz, gm1 * iz, (double)g_depth_n};
+  double du[3] = {gm0 * iz, gm1 * iz, g_depth_n};
   if (!detach_depth) du[2] += -(ux * gm0 + uy * gm1) * iz * iz;
 #pragma unroll
   for (int j = 0; j < 3; ++j) o.gm[j] = (float)(Rc[j * 3] * du[0] + Rc[j * 3 + 1] * du[1] + Rc[j * 3 + 2] * du[2]);
@@ -372,7 +372,7 @@ __device__ __forceinline__ ProjGrad project_bwd_one(uint32_t n, const float *__r
                                                     const float *__restrict__ qvec, const float *__restrict__ svec,
                                                     const float *__restrict__ c2w, int detach_depth,
                                                     const float *__restrict__ g_mean2d,
-                                                    const float *__restrict__ g_cov2d, float g_depth_n) {
+                                                    const float *__restrict__ g_cov2d, double g_depth_n) {
   const float4 g = *reinterpret_cast<const float4 *>(g_cov2d + 4 * (size_t)n);
   const double gc[4] = {(double)g.x, (double)g.y, (double)g.z, (double)g.w};
   return project_bwd_one(n, mean, qvec, svec, c2w, detach_depth, (double)g_mean2d[2 * (size_t)n],
@@ -459,10 +459,10 @@ __device__ __forceinline__ void moments_to_grads_sh(const float *__restrict__ co
   gc[1] = gc[2] = h * (double)mom4[1];
   gc[3] = h * (double)mom4[2];
 }
-// Round 6: a workgroup is 64 Gaussians x 4 VIEW LANES (one wavefront each): wavefront q takes the views q, q + 4, ... of its 64
-// Gaussians, the four partial sums meet in LDS and wavefront 0 writes.  One thread per Gaussian looping over all views (rounds
+// Round 6: a workgroup is 64 Gaussians x kPbvLanes = 2 VIEW LANES (one wavefront each): wavefront q takes the views q, q + 2, ... of
+// its 64 Gaussians, the partial sums meet in LDS and wavefront 0 writes.  One thread per Gaussian looping over all views (rounds
 // 1-5) left a 100 k-Gaussian launch at 1.5 wavefronts per SIMD, each running eight dependent fp64 chains back to back: 43 us per
-// 8 views on MI355X once the chain went to fp64 -- four times the wavefronts, a quarter of the serial work each.
+// 8 views on MI355X once the chain went to fp64 -- twice the wavefronts, half the serial work each.
 constexpr int kPbvThreads = 128;  // (round 6, in flight: 64 / 128 / 256 threads measured -- profiles/r06_notes.md section 20)
 constexpr int kPbvGauss = 64, kPbvLanes = kPbvThreads / kPbvGauss;
 __global__ void __launch_bounds__(kPbvThreads)
@@ -486,12 +486,14 @@ k_project_bwd_views(uint32_t N, const float *__restrict__ mean, const float *__r
       const uint8_t *m = pv.mask[v];
       if (m != nullptr && m[n] == 0) continue;
       const float *ch = pv.g_chan6[v];
-      float gd = pv.g_depth[v] != nullptr ? pv.g_depth[v][n] : 0.f;
+      double gd = pv.g_depth[v] != nullptr ? (double)pv.g_depth[v][n] : 0.0;
       if (ch != nullptr) {  // the depth head and the depth^2 head both feed the view-space depth (include/gsgen_hip.h)
         const float2 *c2 = reinterpret_cast<const float2 *>(ch + 6 * (size_t)n);
         const float2 c01 = c2[0], c23 = c2[1], c45 = c2[2];
         gc[0] += c01.x; gc[1] += c01.y; gc[2] += c23.x;
-        gd = c23.y + 2.0f * pv.depth[v][n] * c45.y;
+        // (in fp64 like the chain it enters: the two heads cancel, and rounded to fp32 their sum cost d mean up to seven times its
+        // per-entry rounding bound -- DESIGN.md section 13)
+        gd = (double)c23.y + 2.0 * (double)pv.depth[v][n] * (double)c45.y;
       }
       ProjGrad o;
       if (moments) {
