@@ -10,7 +10,8 @@
     gsgen_amd.densify    the reference's densify / prune bookkeeping, identical on every rank (pure torch)
     gsgen_amd.io         the reference's checkpoint / .ply / .splat formats
     gsgen_amd.loss       the fused SSIM + L1 / L2 image loss of utils/loss.py (ssim_loss, image_loss, get_image_loss, get_loss_fn)
-                         and its Pearson depth loss (depth_loss, pearson_depth_loss, pearson_depth_loss_terms)
+                         and its Pearson depth loss (depth_loss, pearson_depth_loss, pearson_depth_loss_terms); the trainer's map
+                         regularisers (map_loss, map_loss_terms, sparsity_loss, opague_loss, z_var_loss, get_map_loss)
     gsgen_amd.background the learned MLP background of conf/renderer/mlp_bg.yaml fused with its composite (MLPBackground, mlp_background,
                          mlp_background_images, mlp_background_over)
     gsgen_amd.mesh       marching cubes on the GPU and the mesh export built on it (marching_cubes, density_mesh, mesh_from_ckpt), with vertex
@@ -33,7 +34,8 @@ def __getattr__(name):  # (lazy: importing the package must not import torch)
     if name == "PairListOverflow":
         from .renderer import PairListOverflow
         return PairListOverflow
-    if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn", "depth_loss", "pearson_depth_loss", "pearson_depth_loss_terms"):
+    if name in ("ssim_loss", "image_loss", "get_image_loss", "get_loss_fn", "depth_loss", "pearson_depth_loss", "pearson_depth_loss_terms",
+                "map_loss", "map_loss_terms", "sparsity_loss", "opague_loss", "z_var_loss", "get_map_loss"):
         from . import loss
         return getattr(loss, name)
     if name in ("MLPBackground", "mlp_background", "mlp_background_images", "mlp_background_over"):

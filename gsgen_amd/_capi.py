@@ -149,7 +149,7 @@ SIZE_FUNCS = {
     "gsgen_legacy_sort_workspace_bytes": [u32, u32],
 }
 # entry points bound only where the library has them: the CPU emulator build (oracle/Makefile `emu`) compiles a fixed source list
-# without knn.hip, fps.hip, loss.hip, depth_loss.hip, marching_cubes.hip, background.hip, mesh_sample.hip and guidance_seam.hip, and its tests load it through this class; the in-tree library exports them (EXPORTS, tests/test_cpu_host.py)
+# without knn.hip, fps.hip, loss.hip, depth_loss.hip, marching_cubes.hip, background.hip, mesh_sample.hip, guidance_seam.hip and map_loss.hip, and its tests load it through this class; the in-tree library exports them (EXPORTS, tests/test_cpu_host.py)
 OPTIONAL_SIGNATURES = {
     "gsgen_knn": [vp, u32, u32, vp, vp, vp, sz, vp],
     "gsgen_knn_query": [vp, u32, vp, u32, u32, vp, vp, vp, sz, vp],
@@ -171,6 +171,8 @@ OPTIONAL_SIGNATURES = {
     "gsgen_guidance_input_backward": [vp, i32, i32, u32, u32, u32, u32, u32, u32, f32, vp, vp, sz, vp],
     "gsgen_sds_loss_forward": [vp, u32, u32, i32, f32, vp, vp, sz, vp],
     "gsgen_sds_loss_backward": [u32, u32, vp, vp, vp, sz, vp],
+    "gsgen_map_loss_forward": [vp, vp, u32, u32, vp, vp, vp, vp, sz, vp],
+    "gsgen_map_loss_backward": [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, sz, vp],
 }
 OPTIONAL_SIZE_FUNCS = {
     "gsgen_knn_workspace_bytes": [u32, u32],
@@ -187,6 +189,7 @@ OPTIONAL_SIZE_FUNCS = {
     "gsgen_remove_close_workspace_bytes": [u32],
     "gsgen_guidance_input_workspace_bytes": [u32, u32, u32, u32],
     "gsgen_sds_loss_workspace_bytes": [u32, u32],
+    "gsgen_map_loss_workspace_bytes": [u32],
 }
 EXPORTS = sorted(list(SIGNATURES) + list(SIZE_FUNCS) + list(PTR_FUNCS) + list(OPTIONAL_SIGNATURES) + list(OPTIONAL_SIZE_FUNCS)
                  + ["gsgen_version", "gsgen_error_string", "gsgen_kernel_variant", "gsgen_sh_poly_applies", "gsgen_emit_stage_capacity"])

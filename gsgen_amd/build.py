@@ -33,6 +33,7 @@ SOURCES = {
     "background.hip": ["-ffp-contract=off"],  # every fmaf is explicit: the CPU emulator build performs the GPU's operations (see the file header)
     "mesh_sample.hip": ["-ffp-contract=off"],  # sample points in the stated fp32 order: the CPU emulator build rounds as the GPU does (see the file header)
     "guidance_seam.hip": ["-ffp-contract=off"],  # nothing fused: the CPU emulator build rounds as the GPU does (see the file header)
+    "map_loss.hip": ["-ffp-contract=off"],  # nothing fused: the CPU emulator build rounds as the GPU does (see the file header)
 }
 # -fvisibility=hidden: the dynamic symbol table holds the entry points of include/gsgen_hip.h and nothing else (three
 # cross-file helpers used to be exported beside them)

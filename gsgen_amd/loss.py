@@ -17,6 +17,9 @@ gradient are bit-identical from run to run (no float atomics).
 The depth loss of the image-conditioned step (utils/loss.py:50-66) is here too: `depth_loss` with the reference's signature,
 `pearson_depth_loss` and `pearson_depth_loss_terms` (gsgen_amd/csrc/depth_loss.hip; see the section further down).  It is capturable
 in the same way, with the mask as data, and differentiates with respect to both depth maps.
+
+The regularisers of the text-to-3D step on the rendered opacity and z_var maps (trainer.py:345-382) are the last section:
+`map_loss`, `map_loss_terms`, `sparsity_loss`, `opague_loss`, `z_var_loss` and `get_map_loss` (gsgen_amd/csrc/map_loss.hip).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -281,3 +284,156 @@ def pearson_depth_loss(pred_depth, depth_gt, mask=None):
 def depth_loss(pearson, pred_depth, depth_gt, mask=None):
     """utils/loss.py:50-66 with its signature: `pearson` (there a torchmetrics.PearsonCorrCoef) is ignored and may be None"""
     return pearson_depth_loss(pred_depth, depth_gt, mask)
+
+
+# --- the map regularisers (gsgen_amd/csrc/map_loss.hip) -------------------------------------------------------------------------
+# trainer.py:345-382: sparsity = mean(sqrt(opacity^2 + 0.01)), opague = binary_cross_entropy(c, c) with c = clamp(opacity, 1e-3,
+# 1 - 1e-3) (utils/ops.py:51-55) and z_var = mean(z_var / c * (c > 0.5)), each times a scheduled weight, there some twenty torch
+# launches forward and as many backward.  Here: two launches forward, one backward, no host synchronisation, capturable, and with
+# the weights in a device tensor a replay takes the next step's weights.  DESIGN.md ("Map regularisers") has the definition.
+_MAP_TERMS = ("sparsity", "opague", "z_var")
+
+
+def _map_lib():
+    lib = _capi.load()
+    if not hasattr(lib, "map_loss_forward"):
+        raise RuntimeError(f"{lib.path} was built without the map regulariser kernels (gsgen_amd/csrc/map_loss.hip): rebuild it "
+                           "(python -m gsgen_amd.build)")
+    return lib
+
+
+class _MapLoss(torch.autograd.Function):
+    """opacity, z_var (or None): contiguous float32 maps of one shape; mask: the terms' bits; w_host: three floats; weights: float32
+    [3] on the device or None -> (total 0-dim, terms [3]).  Only the total is differentiable, to opacity and z_var."""
+
+    @staticmethod
+    def forward(ctx, opacity, z_var, mask, w_host, weights):
+        P = opacity.numel()
+        dev = opacity.device
+        lib = _map_lib()
+        ctx.set_materialize_grads(False)
+        nbytes = lib.map_loss_workspace_bytes(P)
+        wsb = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        loss = torch.empty(4, device=dev, dtype=torch.float32)
+        wh = (_capi.f32 * 3)(*w_host)
+        lib.map_loss_forward(opacity.data_ptr(), z_var.data_ptr() if z_var is not None else None, P, mask, wh,
+                             weights.data_ptr() if weights is not None else None, loss.data_ptr(), wsb.data_ptr(), nbytes,
+                             torch.cuda.current_stream(dev).cuda_stream)
+        if ctx.needs_input_grad[0] or (z_var is not None and ctx.needs_input_grad[1]):
+            ctx.save_for_backward(opacity, wsb, *(() if z_var is None else (z_var,)), *(() if weights is None else (weights,)))
+            ctx.args = (P, mask, w_host, nbytes, z_var is not None, weights is not None)
+        total, terms = loss[0], loss[1:]
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, _g_terms):
+        if g_total is None:
+            return None, None, None, None, None
+        P, mask, w_host, nbytes, has_z, has_w = ctx.args
+        opacity, wsb, *rest = ctx.saved_tensors
+        z_var = rest.pop(0) if has_z else None
+        weights = rest.pop(0) if has_w else None
+        g = g_total.to(torch.float32).contiguous()  # (0-dim, on the device: the kernel reads it there)
+        grad_o = torch.empty_like(opacity) if ctx.needs_input_grad[0] else None
+        grad_z = torch.empty_like(z_var) if has_z and ctx.needs_input_grad[1] else None
+        wh = (_capi.f32 * 3)(*w_host)
+        _map_lib().map_loss_backward(opacity.data_ptr(), z_var.data_ptr() if has_z else None, P, mask, wh,
+                                     weights.data_ptr() if has_w else None, g.data_ptr(),
+                                     grad_o.data_ptr() if grad_o is not None else None, grad_z.data_ptr() if grad_z is not None else None,
+                                     wsb.data_ptr(), nbytes, torch.cuda.current_stream(opacity.device).cuda_stream)
+        return grad_o, grad_z, None, None, None
+
+
+def _check_maps(opacity, z_var, w_host, weights):
+    """-> (opacity, z_var or None as [B,H,W] views, the terms' bit mask): nothing copied"""
+    o = _depth_images("opacity", opacity)
+    z = None if z_var is None else _depth_images("z_var", z_var)
+    if z is not None and z.shape != o.shape:
+        raise ValueError(f"gsgen_amd.loss: opacity and z_var differ in shape: {tuple(opacity.shape)} and {tuple(z_var.shape)}")
+    if weights is None:
+        mask = sum(1 << k for k in range(3) if w_host[k] != 0)
+        if mask & 4 and z is None:
+            raise ValueError("gsgen_amd.loss: a z_var weight without z_var: z_var not in output, should turn off the `rgb_only` flag")
+    else:
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (3,):
+            raise ValueError(f"gsgen_amd.loss: weights must be a float32 [3] tensor (sparsity, opague, z_var), got "
+                             f"{tuple(getattr(weights, 'shape', ())) or type(weights)}")
+        if weights.dtype != torch.float32:
+            raise NotImplementedError(f"gsgen_amd.loss: weights must be float32, got {weights.dtype}")
+        if weights.requires_grad:
+            raise NotImplementedError("gsgen_amd.loss: weights require a gradient -- the loss is differentiated with respect to the maps only")
+        mask = 3 if z is None else 7
+    if o.numel() == 0:
+        raise ValueError("gsgen_amd.loss: an empty map has no mean")
+    if o.numel() >= 2 ** 32:
+        raise NotImplementedError(f"gsgen_amd.loss: maps of {o.numel()} pixels -- the kernels take fewer than 2^32")
+    if o.dtype != torch.float32 or (z is not None and z.dtype != torch.float32):
+        raise NotImplementedError(f"gsgen_amd.loss: maps must be float32, got {o.dtype}" + ("" if z is None else f" and {z.dtype}"))
+    tensors = [t for t in (o, z, weights) if t is not None]
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError("gsgen_amd.loss: opacity, z_var and weights must be CUDA (HIP) tensors -- there is no CPU implementation")
+    if any(t.device != o.device for t in tensors):
+        raise ValueError("gsgen_amd.loss: opacity, z_var and weights must be on one device")
+    return o, z, mask
+
+
+def map_loss_terms(opacity, z_var=None, sparsity=0.0, opague=0.0, z_var_weight=0.0, weights=None):
+    """-> (total, terms [3]): total = sparsity * T_s + opague * T_o + z_var_weight * T_z and the three unweighted means (float32, no
+    gradient) from the same launch:
+        T_s = mean(sqrt(opacity^2 + 0.01)),  T_o = mean(-(c log c + (1 - c) log(1 - c))),  T_z = mean(z_var / c * (c > 0.5)),
+    c = clamp(opacity, 1e-3, 1 - 1e-3) (trainer.py:345-382).  The maps are [B,H,W,1], [B,H,W], [H,W,1] or [H,W] float32 of one shape.
+    A term whose weight is 0 is not evaluated and reports 0 (the reference's `> 0.0` tests).  With `weights`, a float32 [3] device
+    tensor, the three Python numbers are ignored, every term whose map is present is evaluated and the weights are read on the device:
+    a captured forward + backward replays with the values then in that tensor.  Autograd reaches opacity and z_var, whichever
+    requires a gradient."""
+    w_host = (float(sparsity), float(opague), float(z_var_weight))
+    o, z, mask = _check_maps(opacity, z_var, w_host, weights)
+    if not o.is_contiguous():
+        o = o.contiguous()
+    if z is not None:
+        if not mask & 4:
+            z = None  # (not read)
+        elif not z.is_contiguous():
+            z = z.contiguous()
+    return _MapLoss.apply(o, z, mask, w_host, None if weights is None else weights.detach())
+
+
+def map_loss(opacity, z_var=None, sparsity=0.0, opague=0.0, z_var_weight=0.0, weights=None):
+    """the total of map_loss_terms (0-dim float32)"""
+    return map_loss_terms(opacity, z_var, sparsity, opague, z_var_weight, weights)[0]
+
+
+def sparsity_loss(opacity):
+    """trainer.py:349: (opacity ** 2 + 0.01).sqrt().mean()"""
+    return map_loss_terms(opacity, sparsity=1.0)[0]
+
+
+def opague_loss(opacity):
+    """trainer.py:361-362: binary_cross_entropy(c, c) with c = opacity.clamp(1e-3, 1 - 1e-3)"""
+    return map_loss_terms(opacity, opague=1.0)[0]
+
+
+def z_var_loss(z_var, opacity):
+    """trainer.py:374-377: (z_var / c * (c > 0.5)).mean() with c = opacity.clamp(1e-3, 1 - 1e-3)"""
+    return map_loss_terms(opacity, z_var, z_var_weight=1.0)[0]
+
+
+def get_map_loss(cfg_loss, max_steps=None):
+    """trainer.py:345-382: -> fn(out, step) -> (loss, {"sparsity", "opague", "z_var"}) from cfg_loss.sparsity, .opague and .z_var (numbers
+    or the reference's scheduled lists, evaluated per step by gsgen_amd.model.schedule_value) on out["opacity"] and out["z_var"] of the
+    model's dict.  Every value returned is a 0-dim device tensor (the three terms unweighted, for the writer): nothing is read back."""
+    from .model import _get, schedule_value
+    specs = [_get(cfg_loss, k, 0.0) for k in _MAP_TERMS]
+
+    def fn(out, step):
+        w = [schedule_value(0.0 if s is None else s, step, max_steps) for s in specs]
+        if not any(w):
+            zero = torch.zeros((), dtype=torch.float32, device=next(iter(out.values())).device)
+            return zero, dict.fromkeys(_MAP_TERMS, zero)
+        if "opacity" not in out:
+            raise ValueError("gsgen_amd.loss: opacity not in output, should turn off the `rgb_only` flag")
+        total, terms = map_loss_terms(out["opacity"], out.get("z_var"), w[0], w[1], w[2])
+        return total, {k: terms[i] for i, k in enumerate(_MAP_TERMS)}
+    return fn

@@ -902,6 +902,35 @@ int gsgen_depth_loss_backward(const float *pred, const float *gt, size_t gt_imag
                               uint32_t B, uint32_t n_pixels, const float *grad_scale_dev, float *grad_pred, float *grad_gt,
                               void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
 
+/* ---- map regularisers: sparsity, opague and z_var (gsgen_amd/csrc/map_loss.hip) -----------------------------------------
+ * replaces trainer.py:345-382: the three regularisers of the text-to-3D step on the rendered maps.  opacity, z_var: device fp32
+ * [n_pixels], contiguous, at any 4-byte alignment (n_pixels = B H W: pixels meet only in the means).  Per pixel, in fp32, with
+ * lo = (float)1e-3, hi = (float)(1.0 - 1e-3), c = clamp(opacity, lo, hi) (a NaN stays), in = lo <= opacity <= hi, m = c > 0.5f:
+ *   sparsity s = sqrtf(opacity^2 + 0.01f);  opague e = -(c logf(c) + (1 - c) logf(1 - c));  z_var z = (z_var / c) * m (a product:
+ *   a non-finite z_var under m == 0 gives NaN, as in torch);  T_k = the mean over the pixels;  total = w_s T_s + w_o T_o + w_z T_z.
+ *   d s / d opacity = opacity / s;  d e / d opacity = in (logf(1 - c) - logf(c));  d z / d z_var = m / c;  d z / d opacity =
+ *   -in m z_var / c^2 (the clamp passes the gradient on its bounds, as torch.clamp does).
+ * terms_mask: bit 0 sparsity, bit 1 opague, bit 2 z_var; a term whose bit is clear is not evaluated (no log without bit 1, z_var
+ *   not read without bit 2), reports 0 and adds nothing to total or to the gradients.  z_var may be NULL without bit 2.
+ * The weights (w_s, w_o, w_z) are weights_host[3], read by the call, or -- when weights_dev is not NULL -- float[3] in device memory
+ *   read by the kernels: a captured forward + backward replays with the weights then in that buffer.  One of the two is required.
+ * forward: loss_out device float[4] = total, T_s, T_o, T_z.  Two launches.
+ * backward: grad_opacity, grad_z_var [n_pixels] = *grad_scale_dev * d total / d opacity, d total / d z_var; either may be NULL; both
+ *   are overwritten (grad_z_var with zeros without bit 2).  It recomputes from the maps: nothing of the forward's is read, the
+ *   workspace is only checked.  The upstream scalar is read on the device.  One launch.
+ * A null opacity, loss_out, grad_scale_dev or workspace, neither weights_host nor weights_dev, a bit above 2 in terms_mask, or bit 2
+ * without z_var: GSGEN_EINVAL; a workspace smaller than the query's answer: GSGEN_EWORKSPACE; a refused call enqueues nothing.
+ * n_pixels == 0: 0 (success), nothing enqueued.  The workspace (24 bytes per 2048 pixels) may be dirty and unaligned: there is no
+ * fill launch.  Per-pixel values are summed in fp64 in a fixed order, no float atomics: loss and gradients are bit-identical from
+ * run to run and do not depend on the alignment of the maps.  Launch shapes from n_pixels alone, no allocation, no host
+ * synchronisation: capturable, and a replay sees the values then in the buffers. */
+size_t gsgen_map_loss_workspace_bytes(uint32_t n_pixels);
+int gsgen_map_loss_forward(const float *opacity, const float *z_var, uint32_t n_pixels, uint32_t terms_mask, const float *weights_host,
+                           const float *weights_dev, float *loss_out, void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
+int gsgen_map_loss_backward(const float *opacity, const float *z_var, uint32_t n_pixels, uint32_t terms_mask, const float *weights_host,
+                            const float *weights_dev, const float *grad_scale_dev, float *grad_opacity, float *grad_z_var,
+                            void *workspace, size_t workspace_bytes, gsgen_stream_t stream);
+
 /* ---- marching cubes over a dense lattice (gsgen_amd/csrc/marching_cubes.hip) -------------------------------------------
  * replaces the PyMCubes call of utils/export.py:123-155.  grid: device fp32 [X][Y][Z], x slowest, contiguous (what
  * gsgen_density_grid writes).  A lattice point is inside iff grid - thresh > 0 in fp32 (NaN: outside), the convention of the

@@ -24,6 +24,7 @@ import scenes  # noqa: E402
 from gsgen_amd import renderer as R  # noqa: E402
 from gsgen_amd.batch import BatchRenderer  # noqa: E402
 from gsgen_amd.optim import FusedAdam  # noqa: E402
+from gsgen_amd.loss import map_loss  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=100_000)
@@ -38,6 +39,8 @@ ap.add_argument("--pipeline", choices=["auto", "on", "off"], default="off", help
 ap.add_argument("--sh", action="store_true", help="SH degree 3 colours through BatchRenderer.render (C = 4, sh_basis='auto') instead of render_heads; "
                                                "with --graph: a captured SH step (gsgen_sh_view::pixel_size_dev)")
 ap.add_argument("--torch-ops", action="store_true", help="activations / z_var as torch operations around render_heads (rounds 1-5) instead of inside its node")
+ap.add_argument("--map-loss", choices=["torch", "fused"], default="torch", help="the sparsity and z_var terms as torch ops (the default: what the numbers "
+                "quoted for this tool were measured with) or as one gsgen_amd.loss.map_loss call (gsgen_amd/csrc/map_loss.hip)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 sc = scenes.pointe_scene(a.n, seed=0, C=4 if a.sh else 1)
@@ -84,7 +87,10 @@ def step(cis=None, c2ws=None):
     else:  # round 6 (what gsgen_amd.model.GaussianSplattingRenderer.forward does): raw parameters in, z_var out
         rgb, dpt, opa, z_var, _ = br.render_heads(P["mean"], P["qvec"], P["svec"], P["alpha"], P["color"], cis, c2ws, bg_rgb=bg, stats=stats,
                                                   z_var=True, activations=("exp", "sigmoid", "sigmoid"))
-    loss = (rgb * g_sds).sum() + 1e-3 * (opa * opa + 0.01).sqrt().mean() + 1e-3 * z_var.mean()  # trainer.py:305-388
+    if a.map_loss == "fused":  # the same two terms of trainer.py:345-382 from one kernel each way (z_var as the reference has it: / c * (c > 0.5))
+        loss = (rgb * g_sds).sum() + map_loss(opa, z_var, sparsity=1e-3, z_var_weight=1e-3)
+    else:
+        loss = (rgb * g_sds).sum() + 1e-3 * (opa * opa + 0.01).sqrt().mean() + 1e-3 * z_var.mean()  # trainer.py:305-388
     loss.backward()
     opt.step()
 
@@ -141,7 +147,7 @@ t1 = time.perf_counter() - t0
 print(json.dumps({"metric": "optimisation-step iters/sec, renderer + optimiser share (guidance stubbed)", "value": a.steps / t1,
                   "unit": "iters/s", "ms_per_iter": 1e3 * t1 / a.steps, "host_ms_per_iter": 1e3 * t_host / a.steps,
                   "views_per_s": a.batch * a.steps / t1, "hipgraph": bool(a.graph) and graph_error is None,
-                  "cameras": "a fresh batch per step (pose and focal length)", "graph_captures": (cs.captures if a.graph and graph_error is None else None), "pipeline": a.pipeline, "hipgraph_error": graph_error,
+                  "cameras": "a fresh batch per step (pose and focal length)", "graph_captures": (cs.captures if a.graph and graph_error is None else None), "pipeline": a.pipeline, "hipgraph_error": graph_error, "map_loss": a.map_loss,
                   "colours": "SH degree 3 (render, C = 4)" if a.sh else "post-activation rgb + heads (render_heads)",
                   "config": {"workload": "BASELINE configs[4] without the diffusion model: 100k Gaussians, "
                                          f"{a.batch} views at {a.res}x{a.res}, " + ("rgb from SH degree 3, " if a.sh else "rgb + depth + opacity + z_var, ") +
